@@ -10,7 +10,13 @@ second for the whole job (all ranks).  A weak-scaling line (batch 100k x N) is r
 at N > 1.  The second half of the metric, gang placements/s, is measured on the same 1M-node
 inventory with a 10k-job mixed PyTorch/MPI/JAX batch (config 3 mix) and reported in "greedy".
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K fit steps and prints the result line (value, ms_per_step,
+the fit roofline).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+Every other line of the bench -- the weak-scaling fit line, the end-to-end / high-cardinality fit
+batches, the aggregation, the greedy line with its roofline, the cfg2-4 configs and the CPU
+baselines -- takes runs of its own and is measured only with --full.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself
 (torch.distributed.run, 127.0.0.1) and exits with their status; it never loads the engine or
@@ -59,6 +65,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every line beside the headline: weak scaling, end-to-end and high-cardinality "
+                         "fit batches, aggregation, greedy, cfg2-4, CPU baselines (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (per-job counts, sampled mask rows) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--nodes", type=int, default=1_000_000)
     ap.add_argument("--fit-jobs", type=int, default=100_000)
     ap.add_argument("--greedy-jobs", type=int, default=10_000)
@@ -81,7 +93,10 @@ def parse_args(argv=None):
     ap.add_argument("--resort-nodes", type=int, default=0, help="pe_config.resort_nodes (0 = default)")
     ap.add_argument("--no-walk-passes", action="store_true",
                     help="skip the greedy roofline's hipEvent passes (warm and cold); used by the profile passes")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run measures the headline only
+        args.no_greedy = args.no_configs = args.no_cpu_baseline = True
+    return args
 
 
 def progress(msg: str):
@@ -377,6 +392,29 @@ def cpu_share() -> int:
     return len(os.sched_getaffinity(0))
 
 
+DUMP_MASK_ROWS = 128   # sampled mask rows of --dump-outputs (1M nodes: 250 KB per row as float64 words)
+
+
+def dump_outputs(eng, dirname: str, rank: int, world: int):
+    """Write what the last fit step left on the device, as a caller of the fit path receives it:
+    fit_counts (per-job feasible-node counts of this rank's shard, float64, exact below 2^53) and a
+    fixed, seeded sample of DUMP_MASK_ROWS rows of the job x node bitmask -- fit_mask_row_index (the
+    sampled jobs) and fit_mask_rows, each row's 64-bit words split into little-endian 32-bit halves so
+    float64 holds them exactly.  The whole mask (12.5 GB at the headline sizes) is not written.  At
+    world > 1 every rank writes its shard's arrays with a _rank<r> suffix."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    counts = eng.fit_counts()
+    J = len(counts)
+    rows = np.sort(np.random.default_rng(0).choice(J, size=min(DUMP_MASK_ROWS, J), replace=False))
+    mask = np.concatenate([eng.fit_mask_rows(int(r), 1) for r in rows]) if J else np.zeros((0, 0), np.uint64)
+    np.save(os.path.join(dirname, f"fit_counts{sfx}.npy"), counts.astype(np.float64))
+    np.save(os.path.join(dirname, f"fit_mask_row_index{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, f"fit_mask_rows{sfx}.npy"),
+            np.ascontiguousarray(mask).view("<u4").astype(np.float64))
+
+
 def fit_path_of(stats: dict, before: dict, blocks: bool) -> str:
     d = {k: stats[k] - before.get(k, 0) for k in stats if isinstance(stats[k], int)}
     if d.get("fit_runs_lds", 0):
@@ -653,6 +691,8 @@ def main(argv=None):
 
     progress("fit headline")
     elapsed, kern_ms, fit_path, feasible = time_fit(req, need, args.steps, args.warmup, "headline")
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
     value = float(N) * J * args.steps / elapsed
     alg = fit_bytes(Ns, J)
     achieved = alg / (kern_ms * 1e-3) / 1e9
@@ -698,7 +738,7 @@ def main(argv=None):
                              "profile step / this run's step - 1): those counters are the profile's, not this run's"},
     }
 
-    if world > 1:
+    if args.full and world > 1:
         # weak scaling beside the strong headline: batch 100k x N, every rank the whole batch
         Jw = args.fit_jobs * world
         wreq, wneed = synth.make_fit_jobs(Jw, synth.SEED["cfg5"])

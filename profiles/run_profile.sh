@@ -12,7 +12,7 @@ OUT=gpurun_out/prof_${TAG}
 mkdir -p $OUT
 BENCH_SMALL="--steps 2 --warmup 1 --no-greedy --no-configs --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- \
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench_trace.json 2> $OUT/trace.err
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench_trace.json 2> $OUT/trace.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o fetch --output-format csv -- \
   python3 bench.py $BENCH_SMALL "$@" > $OUT/bench_fetch.json 2> $OUT/fetch.err
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o write --output-format csv -- \
@@ -23,7 +23,7 @@ timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_SALU SQ_INST_CYCLES_SALU SQ_INSTS_SME
   -d $OUT/sq2 -o sq2 --output-format csv -- python3 bench.py $BENCH_SMALL "$@" > $OUT/bench_sq2.json 2> $OUT/sq2.err
 # greedy walk kernel without the bench's hipEvent passes: warm (as the bench runs) and cold (a 512 MiB
 # buffer rewritten before every walk launch, PE_WALK_FLUSH)
-GREEDY_ONLY="--steps 2 --warmup 1 --no-configs --no-cpu-baseline --no-walk-passes"
+GREEDY_ONLY="--full --steps 2 --warmup 1 --no-configs --no-cpu-baseline --no-walk-passes"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/walk_warm -o walk --output-format csv -- \
   python3 bench.py $GREEDY_ONLY "$@" > $OUT/bench_walk_warm.json 2> $OUT/walk_warm.err
 PE_WALK_FLUSH=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/walk_cold -o walk --output-format csv -- \

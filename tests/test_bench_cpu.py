@@ -147,3 +147,51 @@ def test_greedy_and_aggregation_profile_lookups(tmp_path, monkeypatch):
     assert abs(r["wire_frac"] - 0.5 / 1.5) < 1e-9 and r["wire_bytes"] == 28_000_000
     r = bench.agg_roofline(42_000_000, 14_000_000, 4.0, 3.9, None, None)
     assert r["call_ms"] == 4.0 and r["frac"] is None and r["peak"] is None
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full every line beside the headline is off; --full restores them (and the --no-*
+    options still trim a full run)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.no_greedy and a.no_configs and a.no_cpu_baseline
+    assert a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    f = bench.parse_args(["--full"])
+    assert f.full and not (f.no_greedy or f.no_configs or f.no_cpu_baseline)
+    f = bench.parse_args(["--full", "--no-greedy", "--dump-outputs", "d"])
+    assert f.no_greedy and not f.no_configs and f.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_counts_and_sampled_rows(tmp_path):
+    """dump_outputs: float64 arrays, the same seeded row sample every run, mask words split into exact
+    32-bit halves."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    class FakeEngine:
+        J, W = 300, 3
+        mask = np.random.default_rng(5).integers(0, 2**64, size=(J, W), dtype=np.uint64)
+
+        def fit_counts(self):
+            return np.arange(self.J, dtype=np.int64) * 3
+
+        def fit_mask_rows(self, row0, n):
+            return self.mask[row0:row0 + n].copy()
+
+    for d in ("a", "b"):
+        bench.dump_outputs(FakeEngine(), str(tmp_path / d), 0, 1)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("fit_counts", "fit_mask_row_index", "fit_mask_rows")}
+    for n, a in got.items():
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert np.array_equal(got["fit_counts"], np.arange(300) * 3.0)
+    rows = got["fit_mask_row_index"].astype(np.int64)
+    assert len(rows) == bench.DUMP_MASK_ROWS and len(set(rows)) == len(rows) and np.all(np.diff(rows) > 0)
+    halves = got["fit_mask_rows"].astype(np.uint64)
+    assert halves.shape == (len(rows), 6)
+    assert np.array_equal(halves[:, 0::2] | (halves[:, 1::2] << np.uint64(32)), FakeEngine.mask[rows])
+    bench.dump_outputs(FakeEngine(), str(tmp_path / "r"), 1, 2)      # ranks of a sharded run do not collide
+    assert sorted(os.listdir(tmp_path / "r")) == ["fit_counts_rank1.npy", "fit_mask_row_index_rank1.npy",
+                                                  "fit_mask_rows_rank1.npy"]

@@ -25,7 +25,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--nodes", "100000", "--fit-jobs", "5000", "--greedy-jobs", "1000", "--agg-jobs", "20000", "--steps", "3",
-        "--warmup", "1", "--greedy-steps", "2", "--no-cpu-baseline"]
+        "--warmup", "1", "--greedy-steps", "2", "--full", "--no-cpu-baseline"]
 
 
 def _bench(gpus, extra_env):

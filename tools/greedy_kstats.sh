@@ -9,7 +9,7 @@ for lib in "$@"; do
   d=gpurun_out/gks_$i
   rm -rf $d
   PE_LIBRARY=${lib:+$PWD/$lib} timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o k --output-format csv -- \
-    python3 bench.py --steps 1 --warmup 1 --no-configs --no-cpu-baseline --no-walk-passes --greedy-steps 3 > $d.json 2> $d.err
+    python3 bench.py --full --steps 1 --warmup 1 --no-configs --no-cpu-baseline --no-walk-passes --greedy-steps 3 > $d.json 2> $d.err
   python3 - "$lib" $d <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[2] + "/**/*kernel_stats.csv", recursive=True)[0]

@@ -1,5 +1,5 @@
 for tk in 32 64 128 256; do for wg in 32 64 128; do
-  line=$(timeout -k 10 120 python bench.py --no-cpu-baseline --no-configs --steps 1 --warmup 0 --greedy-steps 2 --topk $tk --window-groups $wg)
+  line=$(timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-configs --steps 1 --warmup 0 --greedy-steps 2 --topk $tk --window-groups $wg)
   python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); g=d['greedy']

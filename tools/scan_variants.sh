@@ -7,7 +7,7 @@ for lib in "$@"; do
   out=gpurun_out/scanvar_$(basename $lib .so)
   rm -rf $out
   PE_LIBRARY=$PWD/build_variants/$lib timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out -o t --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --steps 1 --warmup 0 --greedy-steps 2 $SCANVAR_ARGS > $out.json 2> $out.err
+    python3 bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --greedy-steps 2 $SCANVAR_ARGS > $out.json 2> $out.err
   python3 - "$lib" "$out" <<'PY'
 import csv, glob, json, sys
 lib, out = sys.argv[1], sys.argv[2]

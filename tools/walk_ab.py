@@ -12,7 +12,7 @@ for rep in range(2):
         env = dict(os.environ)
         if lib:
             env["PE_LIBRARY"] = os.path.abspath(lib)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-configs",
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-configs",
                             "--steps", "1", "--warmup", "1", "--greedy-steps", "3"], env=env, capture_output=True,
                            text=True, timeout=300, cwd=ROOT)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
