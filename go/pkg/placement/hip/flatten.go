@@ -14,6 +14,7 @@ import (
 	"fmt"
 	"math/big"
 
+	inf "gopkg.in/inf.v0"
 	corev1 "k8s.io/api/core/v1"
 	"k8s.io/apimachinery/pkg/api/resource"
 )
@@ -218,6 +219,87 @@ func (a *KeyAgg) Unflatten(j int, formats map[corev1.ResourceName]resource.Forma
 			q.Format = f
 		}
 		out[a.Keys[k]] = q
+	}
+	return out
+}
+
+// scaledBig is q / 10^s when that is an exact integer >= 0, of any size.
+func scaledBig(q resource.Quantity, s int32) (*big.Int, bool) {
+	d := q.AsDec()
+	u := new(big.Int).Set(d.UnscaledBig())
+	if u.Sign() < 0 {
+		return nil, false
+	}
+	k := -int32(d.Scale()) - s // q / 10^s = u * 10^k
+	if k >= 0 {
+		u.Mul(u, new(big.Int).Exp(big.NewInt(10), big.NewInt(int64(k)), nil))
+	} else {
+		r := new(big.Int)
+		u.QuoRem(u, new(big.Int).Exp(big.NewInt(10), big.NewInt(int64(-k)), nil), r)
+		if r.Sign() != 0 {
+			return nil, false
+		}
+	}
+	return u, true
+}
+
+var (
+	two64  = new(big.Int).Lsh(big.NewInt(1), 64)
+	mask64 = new(big.Int).Sub(two64, big.NewInt(1))
+)
+
+// scaledLimbs converts every entry to its key's scale as the two limbs of pe_pg_min_resources_wide
+// (value = hi * 2^64 + lo): a value with no int64 at its scale travels instead of flagging its job.
+// wide reports whether any entry needs the hi limbs (hi != 0 or lo >= 2^63); only a negative value or
+// one of 2^127 and more -- which the engine does not take -- flags its job (jobBad).
+func (b *KeyCSR) scaledLimbs(scale []int32) (lo, hi []uint64, jobBad []uint8, wide bool) {
+	J := len(b.JobGroupOff) - 1
+	lo = make([]uint64, len(b.EntQ))
+	hi = make([]uint64, len(b.EntQ))
+	jobBad = make([]uint8, J)
+	for j := 0; j < J; j++ {
+		for g := b.JobGroupOff[j]; g < b.JobGroupOff[j+1]; g++ {
+			for c := b.GroupContOff[g]; c < b.GroupContOff[g+1]; c++ {
+				for x := b.EntOff[c]; x < b.EntOff[c+1]; x++ {
+					v, ok := scaledBig(b.EntQ[x], scale[b.EntKey[x]])
+					if !ok || v.BitLen() > 127 {
+						jobBad[j] = 1
+						continue
+					}
+					lo[x] = new(big.Int).And(v, mask64).Uint64()
+					hi[x] = new(big.Int).Rsh(v, 64).Uint64()
+					if hi[x] != 0 || lo[x]>>63 != 0 {
+						wide = true
+					}
+				}
+			}
+		}
+	}
+	return lo, hi, jobBad, wide
+}
+
+// Value is job j's sum of key k as the signed 128-bit integer Hi * 2^64 + Lo, a count of 10^Scale[k].
+func (a *KeyAggWide) Value(j, k int) *big.Int {
+	i := j*len(a.Keys) + k
+	v := new(big.Int).Lsh(big.NewInt(a.Hi[i]), 64)
+	return v.Add(v, new(big.Int).SetUint64(a.Lo[i]))
+}
+
+// Unflatten turns job j's result back into a ResourceList like (*KeyAgg).Unflatten, each quantity
+// built from the inf.Dec of the two limbs at the key's scale -- what the reference's Quantity holds
+// once a sum has left int64 (util.go:83-86, coscheduling.go:113-115).
+func (a *KeyAggWide) Unflatten(j int, formats map[corev1.ResourceName]resource.Format) corev1.ResourceList {
+	nk := len(a.Keys)
+	out := corev1.ResourceList{}
+	for k := 0; k < nk; k++ {
+		if !a.Present[j*nk+k] {
+			continue
+		}
+		f := resource.DecimalSI
+		if ff, ok := formats[a.Keys[k]]; ok {
+			f = ff
+		}
+		out[a.Keys[k]] = *resource.NewDecimalQuantity(*inf.NewDecBig(a.Value(j, k), inf.Scale(-a.Scale[k])), f)
 	}
 	return out
 }

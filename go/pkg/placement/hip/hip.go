@@ -452,6 +452,100 @@ func (e *Engine) PGMinResourcesKeys(mode int, b *KeyCSR) (*KeyAgg, error) {
 	return out, nil
 }
 
+// KeyAggWide is the result of PGMinResourcesWide: KeyAgg with every sum as a signed 128-bit integer.
+type KeyAggWide struct {
+	Keys     []corev1.ResourceName
+	Scale    []int32  // per key: values are counts of 10^Scale
+	Lo       []uint64 // [J][len(Keys)] low limb
+	Hi       []int64  // [J][len(Keys)] high limb (two's complement: the sign extension when Overflow is 0)
+	Present  []bool   // [J][len(Keys)] (keys with value 0 included)
+	Members  []int32
+	Overflow []uint8 // 0 = the int64 path answered, 1 = exact 128-bit value, 2 = no 128-bit answer (values 0)
+}
+
+// PGMinResourcesWide is PGMinResourcesKeys with an exact answer past int64 (pe_pg_min_resources_wide):
+// a value with no int64 at its key's scale travels as two limbs, and a job whose sums leave int64 is
+// summed by the engine's 128-bit kernel instead of being flagged for the reference.  Overflow[j] is 2
+// only for a job with no 128-bit answer (or a value the engine does not take); that job's values are 0.
+func (e *Engine) PGMinResourcesWide(mode int, b *KeyCSR) (*KeyAggWide, error) {
+	J := len(b.JobGroupOff) - 1
+	if J < 0 {
+		return nil, errors.New("placement: JobGroupOff needs J+1 entries")
+	}
+	nk := len(b.Keys)
+	out := &KeyAggWide{Keys: b.Keys, Scale: b.Scales(), Lo: make([]uint64, J*nk), Hi: make([]int64, J*nk),
+		Present: make([]bool, J*nk), Members: make([]int32, J), Overflow: make([]uint8, J)}
+	if J == 0 {
+		return out, nil
+	}
+	vlo, vhi, jobBad, wide := b.scaledLimbs(out.Scale)
+	nc := len(b.ContKind)
+	flags := make([]uint32, nc)
+	pres := make([]uint16, J)
+	ovf := make([]uint8, J)
+	for lo := 0; lo < nk || (lo == 0 && nk == 0); lo += MaxKeys {
+		n := nk - lo
+		if n > MaxKeys {
+			n = MaxKeys
+		}
+		if n < 1 {
+			n = 1 // no key at all: one empty key, for Members
+		}
+		reqLo := make([]uint64, nc*n)
+		var reqHi []uint64 // stays nil (NULL) when every value of the batch is an int64
+		if wide {
+			reqHi = make([]uint64, nc*n)
+		}
+		resLo := make([]uint64, J*n)
+		resHi := make([]int64, J*n)
+		for c := 0; c < nc; c++ {
+			f := uint32(b.ContKind[c]) << KeysKindShift
+			for x := b.EntOff[c]; x < b.EntOff[c+1]; x++ {
+				k := int(b.EntKey[x]) - lo
+				if k < 0 || k >= n || lo+k >= nk {
+					continue
+				}
+				reqLo[c*n+k] = vlo[x]
+				if wide {
+					reqHi[c*n+k] = vhi[x]
+				}
+				f |= 1 << uint(k)
+			}
+			flags[c] = f
+		}
+		rc := C.pe_pg_min_resources_wide(e.ctx, C.int32_t(mode), C.int64_t(J), C.int32_t(n), ptr32(b.JobGroupOff),
+			ptr32(b.MinMember), ptr32(b.GroupReplicas), ptr32(b.GroupContOff), ptru64(reqLo), ptru64(reqHi), ptru32(flags),
+			ptru64(resLo), ptr64(resHi), (*C.uint16_t)(unsafe.Pointer(&pres[0])), ptr32(out.Members), ptr8(ovf))
+		if rc != C.PE_OK && rc != C.PE_EOVERFLOW {
+			return nil, e.err(rc, "pe_pg_min_resources_wide")
+		}
+		for j := 0; j < J; j++ {
+			if ovf[j] > out.Overflow[j] {
+				out.Overflow[j] = ovf[j]
+			}
+			for k := 0; k < n && lo+k < nk; k++ {
+				out.Lo[j*nk+lo+k] = resLo[j*n+k]
+				out.Hi[j*nk+lo+k] = resHi[j*n+k]
+				out.Present[j*nk+lo+k] = pres[j]>>uint(k)&1 != 0
+			}
+		}
+		if nk == 0 {
+			break
+		}
+	}
+	for j := 0; j < J; j++ {
+		if jobBad[j] != 0 {
+			out.Overflow[j] = 2
+		}
+		if out.Overflow[j] == 2 { // no answer in one key slice: none for the job
+			for k := 0; k < nk; k++ {
+				out.Lo[j*nk+k], out.Hi[j*nk+k] = 0, 0
+			}
+		}
+	}
+	return out, nil
+}
+
 // FitMask evaluates every job against every node of the shard (device-resident mask); returns the
 // per-job feasible counts of this shard and the mask's words per row.
 func (e *Engine) FitMask(req []int64, need []uint32) (counts []int64, wordsPerRow int64, err error) {

@@ -28,7 +28,8 @@
  * Units (canonical int64): dim 0 cpu in milli-cores, dim 1 memory in
  * bytes, dim 2 accelerator count (resource name given by pe_config.gpu_resource_name), dim 3
  * ephemeral-storage in bytes.  Values must be >= 0; int64 overflow is flagged, never wrapped
- * (where Go's resource.Quantity would fall back to inf.Dec).
+ * (where Go's resource.Quantity would fall back to inf.Dec); pe_pg_min_resources_wide answers those
+ * jobs exactly in 128 bits.
  *
  * Ownership: the caller owns every host pointer for the duration of the call only; the library
  * never retains them.  Device memory is library-owned; pointers it hands out stay valid until
@@ -168,6 +169,8 @@ typedef struct {
   int64_t agg_segments;
   int64_t agg_narrow_segments;
   int64_t agg_wire_bytes;
+  /* (ABI 7, additive) jobs answered by the 128-bit aggregation kernel (pe_pg_min_resources_wide), cumulative */
+  int64_t agg_wide_jobs;
 } pe_stats;
 
 int pe_abi_version(void);
@@ -247,6 +250,31 @@ int pe_pg_min_resources(pe_ctx* ctx, int32_t mode, int64_t n_jobs, const int32_t
 int pe_pg_min_resources_keys(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t n_keys, const int32_t* job_group_off,
                              const int32_t* min_member, const int32_t* group_replicas, const int32_t* group_cont_off,
                              const int64_t* cont_req, const uint32_t* cont_flags, int64_t* out_min_res,
+                             uint16_t* out_present, int32_t* out_members, uint8_t* out_overflow);
+
+/* (ABI 7, additive) The key-table aggregation with an exact answer past int64 -- what the reference
+ * holds in inf.Dec (util.go:83-86,98-101 Quantity.Add; coscheduling.go:113-115 Quantity.Mul).  Key
+ * table, flags, modes, n_keys limits and PE_EINVAL rules are those of pe_pg_min_resources_keys.
+ * Inputs: a request is the non-negative 128-bit integer hi * 2^64 + lo.
+ *   cont_req_hi == NULL: hi = 0 and lo is read as int64; a negative lo is PE_EINVAL (first index in
+ *                        pe_last_error), as in pe_pg_min_resources_keys.
+ *   cont_req_hi != NULL: lo is a full uint64 and hi must be < 2^63, else PE_EINVAL with the index.  This
+ *                        is how a value with no int64 at its key's scale travels.
+ * Result per (job, key): the exact sum as a signed two's-complement 128-bit integer out_hi:out_lo
+ * (signed: V2 multiplies by the int32 replica count, which may be negative).  out_overflow[j]:
+ *   0  the int64 path answered: out_lo is bit-equal to pe_pg_min_resources_keys' out_min_res and
+ *      out_hi is its sign extension
+ *   1  some int64 step overflowed, or an input was wider than int64 (hi != 0, or lo >= 2^63 with hi
+ *      given): the value is the exact 128-bit one, summed on the device by the 128-bit kernel
+ *   2  some intermediate left [-2^127, 2^127) (sticky per job): that job's values are defined as 0
+ * out_present / out_members are exact in every case.  Returns PE_OK unless some job is 2; then
+ * PE_EOVERFLOW with every output still written.  Only the jobs that need it (flag != 0) are gathered
+ * into a compact sub-batch for the 128-bit kernel; every other job of the batch takes the int64 path
+ * of pe_pg_min_resources_keys, and a batch without such a job is that call. */
+int pe_pg_min_resources_wide(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t n_keys, const int32_t* job_group_off,
+                             const int32_t* min_member, const int32_t* group_replicas, const int32_t* group_cont_off,
+                             const uint64_t* cont_req_lo /*[C][n_keys]*/, const uint64_t* cont_req_hi /*[C][n_keys] or NULL*/,
+                             const uint32_t* cont_flags, uint64_t* out_lo /*[J][n_keys]*/, int64_t* out_hi /*[J][n_keys]*/,
                              uint16_t* out_present, int32_t* out_members, uint8_t* out_overflow);
 
 /* What-if feasibility (config 5): bit (j, n) = fit(job j, node n) against the CURRENT residuals

@@ -408,6 +408,13 @@ struct pe_ctx {
   DevBuf<int32_t> a_jgo, a_mm, a_rep, a_gco, a_mem;
   DevBuf<int64_t> a_req, a_out;
   DevBuf<uint8_t> a_fl, a_pres, a_ovf;
+  // 128-bit aggregation (pe_pg_min_resources_wide): the gathered sub-batch, its device copy (inputs then
+  // outputs) and the outputs read back; the jobs that go wide, the per-job wide-input marks and the
+  // int64 pass's copy of the low limbs with those jobs zeroed.  Grow and are reused.
+  HostBuf<uint8_t> aw_stage, aw_outh;
+  DevBuf<uint8_t> aw_dev;
+  std::vector<int64_t> aw_jobs, aw_lo;
+  std::vector<uint8_t> aw_mark;
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -477,6 +484,7 @@ struct pe_ctx {
     a_dstage.release();
     a_jgo.release(); a_mm.release(); a_rep.release(); a_gco.release(); a_mem.release();
     a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
+    aw_stage.release(); aw_outh.release(); aw_dev.release();
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
     g_upd.release(); g_kn.release(); g_lo.release(); h_groups.release(); h_groups2.release(); h_out.release(); h_out2.release(); h_own.release(); h_merged.release(); h_upd.release();
     for (auto& x : h_xg) x.release();
@@ -1116,7 +1124,8 @@ void ensure_pinned(HostBuf<T>& b, size_t count, const char* what) {
 // to the device and launched one after another (below).
 // ak / n_keys: the fixed four dimensions ({4, 1}, n_keys 4) or a per-call key table of n_keys <= 16
 // keys padded to ak.nd (pe_pg_min_resources_keys); cont_flags / out_present are u8 or u32 / u16.
-int agg_call(pe_ctx* ctx, int32_t mode, int64_t n_jobs, pe::AggKeys ak, int n_keys, const int32_t* job_group_off,
+// agg_call_locked: the call's body, run under the context's lock (guarded); errors are raised.
+int agg_call_locked(pe_ctx* ctx, int32_t mode, int64_t n_jobs, pe::AggKeys ak, int n_keys, const int32_t* job_group_off,
                     const int32_t* min_member, const int32_t* group_replicas, const int32_t* group_cont_off,
                     const int64_t* cont_req, const void* cont_flags_v, int64_t* out_min_res, void* out_present_v,
                     int32_t* out_members, uint8_t* out_overflow) {
@@ -1125,7 +1134,7 @@ int agg_call(pe_ctx* ctx, int32_t mode, int64_t n_jobs, pe::AggKeys ak, int n_ke
   const bool wide = ak.fb != 1;
   const int ND = ak.nd;
   const int pb = wide ? 2 : 1;   // presence bytes per job out
-  return guarded(ctx, [&]() -> int {
+  {
     if (mode != PE_MODE_V1 && mode != PE_MODE_V2) raise(PE_EINVAL, "mode must be PE_MODE_V1 or PE_MODE_V2");
     if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
     if (n_jobs == 0) return PE_OK;
@@ -1507,7 +1516,116 @@ int agg_call(pe_ctx* ctx, int32_t mode, int64_t n_jobs, pe::AggKeys ak, int n_ke
       return PE_EOVERFLOW;
     }
     return PE_OK;
+  }
+}
+
+int agg_call(pe_ctx* ctx, int32_t mode, int64_t n_jobs, pe::AggKeys ak, int n_keys, const int32_t* job_group_off,
+             const int32_t* min_member, const int32_t* group_replicas, const int32_t* group_cont_off,
+             const int64_t* cont_req, const void* cont_flags_v, int64_t* out_min_res, void* out_present_v,
+             int32_t* out_members, uint8_t* out_overflow) {
+  return guarded(ctx, [&]() -> int {
+    return agg_call_locked(ctx, mode, n_jobs, ak, n_keys, job_group_off, min_member, group_replicas, group_cont_off,
+                           cont_req, cont_flags_v, out_min_res, out_present_v, out_members, out_overflow);
   });
+}
+
+// pe_pg_min_resources_wide, the 128-bit pass: gather jobs `jobs` (ascending) of the caller's batch into a
+// compact CSR sub-batch with rebased offsets and both limbs, upload it, run pg_agg_wide_kernel (one
+// lane per (job, key) pair) and scatter the results into the caller's arrays.  Every sum happens on the
+// device; the host only moves records.  out_overflow[j] becomes 1, or 2 where a pair of the job left
+// [-2^127, 2^127) (the job's values are then 0).  Returns whether some job is 2.
+bool agg_wide_pass(pe_ctx* ctx, int32_t mode, int n_keys, const int32_t* job_group_off, const int32_t* min_member,
+                   const int32_t* group_replicas, const int32_t* group_cont_off, const uint64_t* lo,
+                   const uint64_t* hi, const uint32_t* cont_flags, const std::vector<int64_t>& jobs, uint64_t* out_lo,
+                   int64_t* out_hi, uint8_t* out_overflow) {
+  const int64_t nw = (int64_t)jobs.size();
+  const bool v1 = mode == PE_MODE_V1;
+  int64_t G = 0, C = 0;
+  for (const int64_t j : jobs) {
+    const int32_t g0 = job_group_off[j], g1 = job_group_off[j + 1];
+    G += g1 - g0;
+    if (g1 > g0) C += group_cont_off[g1] - group_cont_off[g0];
+  }
+  // sections (16-B aligned): inputs jgo, min_member, replicas, gco, lo, hi, flags; outputs lo, hi, flags
+  int64_t off[11];
+  off[0] = 0;
+  off[1] = off[0] + pe::agg_r16((nw + 1) * 4);
+  off[2] = off[1] + (v1 ? pe::agg_r16(nw * 4) : 0);
+  off[3] = off[2] + pe::agg_r16(G * 4);
+  off[4] = off[3] + pe::agg_r16((G + 1) * 4);
+  off[5] = off[4] + pe::agg_r16(C * n_keys * 8);
+  off[6] = off[5] + (hi ? pe::agg_r16(C * n_keys * 8) : 0);
+  off[7] = off[6] + pe::agg_r16(C * 4);            // end of the inputs
+  off[8] = off[7] + pe::agg_r16(nw * n_keys * 8);
+  off[9] = off[8] + pe::agg_r16(nw * n_keys * 8);
+  off[10] = off[9] + pe::agg_r16(nw * n_keys);
+  const int64_t in_bytes = off[7], out_bytes = off[10] - off[7];
+  ensure_pinned(ctx->aw_stage, (size_t)in_bytes, "alloc pinned wide batch");
+  ensure_pinned(ctx->aw_outh, (size_t)out_bytes, "alloc pinned wide outputs");
+  if ((size_t)off[10] > ctx->aw_dev.n)
+    hipchk(ctx->aw_dev.ensure(std::max((size_t)off[10], ctx->aw_dev.n + ctx->aw_dev.n / 2)), "alloc device wide batch");
+  uint8_t* b = ctx->aw_stage.p;
+  int32_t* s_jgo = reinterpret_cast<int32_t*>(b + off[0]);
+  int32_t* s_mm = reinterpret_cast<int32_t*>(b + off[1]);
+  int32_t* s_rep = reinterpret_cast<int32_t*>(b + off[2]);
+  int32_t* s_gco = reinterpret_cast<int32_t*>(b + off[3]);
+  uint64_t* s_lo = reinterpret_cast<uint64_t*>(b + off[4]);
+  uint64_t* s_hi = reinterpret_cast<uint64_t*>(b + off[5]);
+  uint32_t* s_fl = reinterpret_cast<uint32_t*>(b + off[6]);
+  int64_t g = 0, c = 0;
+  s_jgo[0] = 0;
+  s_gco[0] = 0;
+  for (int64_t w = 0; w < nw; ++w) {
+    const int64_t j = jobs[(size_t)w];
+    const int32_t g0 = job_group_off[j], g1 = job_group_off[j + 1];
+    if (v1) s_mm[w] = min_member[j];
+    if (g1 > g0) {
+      const int32_t c0 = group_cont_off[g0], c1 = group_cont_off[g1];
+      std::memcpy(s_rep + g, group_replicas + g0, (size_t)(g1 - g0) * 4);
+      for (int32_t q = g0; q < g1; ++q) s_gco[g + (q - g0) + 1] = (int32_t)(c + (group_cont_off[q + 1] - c0));
+      if (c1 > c0) {
+        std::memcpy(s_lo + c * n_keys, lo + (int64_t)c0 * n_keys, (size_t)(c1 - c0) * n_keys * 8);
+        if (hi) std::memcpy(s_hi + c * n_keys, hi + (int64_t)c0 * n_keys, (size_t)(c1 - c0) * n_keys * 8);
+        std::memcpy(s_fl + c, cont_flags + c0, (size_t)(c1 - c0) * 4);
+      }
+      g += g1 - g0;
+      c += c1 - c0;
+    }
+    s_jgo[w + 1] = (int32_t)g;
+  }
+  uint8_t* d = ctx->aw_dev.p;
+  hipchk(hipMemcpyAsync(d, b, (size_t)in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D wide batch");
+  hipchk(pe::launch_pg_agg_wide(ctx->stream, mode, nw, n_keys, reinterpret_cast<const int32_t*>(d + off[0]),
+                                v1 ? reinterpret_cast<const int32_t*>(d + off[1]) : nullptr,
+                                reinterpret_cast<const int32_t*>(d + off[2]),
+                                reinterpret_cast<const int32_t*>(d + off[3]),
+                                reinterpret_cast<const uint64_t*>(d + off[4]),
+                                hi ? reinterpret_cast<const uint64_t*>(d + off[5]) : nullptr,
+                                reinterpret_cast<const uint32_t*>(d + off[6]), reinterpret_cast<uint64_t*>(d + off[7]),
+                                reinterpret_cast<int64_t*>(d + off[8]), d + off[9]),
+         "launch pg_agg_wide");
+  hipchk(hipMemcpyAsync(ctx->aw_outh.p, d + off[7], (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream),
+         "D2H wide outputs");
+  hipchk(hipStreamSynchronize(ctx->stream), "sync pg_agg_wide");
+  ctx->stats.agg_wide_jobs += nw;
+  const uint64_t* r_lo = reinterpret_cast<const uint64_t*>(ctx->aw_outh.p);
+  const int64_t* r_hi = reinterpret_cast<const int64_t*>(ctx->aw_outh.p + (off[8] - off[7]));
+  const uint8_t* r_fl = ctx->aw_outh.p + (off[9] - off[7]);
+  bool any2 = false;
+  for (int64_t w = 0; w < nw; ++w) {
+    const int64_t j = jobs[(size_t)w];
+    const bool left = std::memchr(r_fl + w * n_keys, 1, (size_t)n_keys) != nullptr;
+    if (left) {
+      std::memset(out_lo + j * n_keys, 0, (size_t)n_keys * 8);
+      std::memset(out_hi + j * n_keys, 0, (size_t)n_keys * 8);
+    } else {
+      std::memcpy(out_lo + j * n_keys, r_lo + w * n_keys, (size_t)n_keys * 8);
+      std::memcpy(out_hi + j * n_keys, r_hi + w * n_keys, (size_t)n_keys * 8);
+    }
+    out_overflow[j] = left ? 2 : 1;
+    any2 |= left;
+  }
+  return any2;
 }
 
 }  // namespace
@@ -1533,6 +1651,86 @@ int pe_pg_min_resources_keys(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t 
   const pe::AggKeys ak{n_keys <= 4 ? 4 : n_keys <= 8 ? 8 : 16, 4};
   return agg_call(ctx, mode, n_jobs, ak, n_keys, job_group_off, min_member, group_replicas, group_cont_off, cont_req,
                   cont_flags, out_min_res, out_present, out_members, out_overflow);
+}
+
+// The int64 pass of pe_pg_min_resources_keys over the whole batch, then the 128-bit pass over the jobs
+// it flagged plus the jobs holding an input wider than int64 (agg_wide_pass).  Without such a job the
+// call is the keys call, the sign extension into out_hi and a memchr.
+int pe_pg_min_resources_wide(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t n_keys, const int32_t* job_group_off,
+                             const int32_t* min_member, const int32_t* group_replicas, const int32_t* group_cont_off,
+                             const uint64_t* cont_req_lo, const uint64_t* cont_req_hi, const uint32_t* cont_flags,
+                             uint64_t* out_lo, int64_t* out_hi, uint16_t* out_present, int32_t* out_members,
+                             uint8_t* out_overflow) {
+  if (n_keys < 1 || n_keys > PE_MAX_KEYS) {
+    if (ctx) ctx->err = "n_keys must be in [1, " + std::to_string(PE_MAX_KEYS) + "]";
+    return PE_EINVAL;
+  }
+  const pe::AggKeys ak{n_keys <= 4 ? 4 : n_keys <= 8 ? 8 : 16, 4};
+  return guarded(ctx, [&]() -> int {
+    const int64_t* narrow_req = reinterpret_cast<const int64_t*>(cont_req_lo);
+    bool wide_in = false;
+    if (cont_req_hi && n_jobs > 0) {
+      // the wide-input scan walks the offsets: the checks agg_call_locked makes on them come first
+      if (mode != PE_MODE_V1 && mode != PE_MODE_V2) raise(PE_EINVAL, "mode must be PE_MODE_V1 or PE_MODE_V2");
+      need_ptr(job_group_off, "job_group_off");
+      check_offsets(job_group_off, n_jobs, -1, "job_group_off");
+      const int64_t G = job_group_off[n_jobs];
+      if (G > 0) {
+        need_ptr(group_cont_off, "group_cont_off");
+        check_offsets(group_cont_off, G, -1, "group_cont_off");
+      }
+      const int64_t C = G > 0 ? group_cont_off[G] : 0;
+      if (C > 0) need_ptr(cont_req_lo, "cont_req_lo");
+      auto& mark = ctx->aw_mark;
+      mark.assign((size_t)n_jobs, 0);
+      for (int64_t j = 0; j < n_jobs && C > 0; ++j) {
+        const int64_t i0 = (int64_t)group_cont_off[job_group_off[j]] * n_keys;
+        const int64_t i1 = (int64_t)group_cont_off[job_group_off[j + 1]] * n_keys;
+        uint64_t any = 0, any_hi = 0;
+        for (int64_t i = i0; i < i1; ++i) {
+          any_hi |= cont_req_hi[i];
+          any |= cont_req_hi[i] | (cont_req_lo[i] >> 63);
+        }
+        if (any_hi >> 63)
+          for (int64_t i = i0; i < i1; ++i)
+            if (cont_req_hi[i] >> 63)
+              raise(PE_EINVAL, "cont_req_hi: request of 2^127 or more at index " + std::to_string(i));
+        if (any) mark[(size_t)j] = 1, wide_in = true;
+      }
+      if (wide_in) {   // those jobs reach the int64 kernels as zeros; their int64 outputs are not used
+        auto& cp = ctx->aw_lo;
+        cp.resize((size_t)(C * n_keys));
+        std::memcpy(cp.data(), cont_req_lo, (size_t)(C * n_keys) * 8);
+        for (int64_t j = 0; j < n_jobs; ++j)
+          if (mark[(size_t)j]) {
+            const int64_t i0 = (int64_t)group_cont_off[job_group_off[j]] * n_keys;
+            const int64_t i1 = (int64_t)group_cont_off[job_group_off[j + 1]] * n_keys;
+            std::memset(cp.data() + i0, 0, (size_t)(i1 - i0) * 8);
+          }
+        narrow_req = cp.data();
+      }
+    }
+    if (n_jobs > 0) need_ptr(out_hi, "out_hi");
+    const int rc = agg_call_locked(ctx, mode, n_jobs, ak, n_keys, job_group_off, min_member, group_replicas,
+                                   group_cont_off, narrow_req, cont_flags, reinterpret_cast<int64_t*>(out_lo),
+                                   out_present, out_members, out_overflow);
+    if (n_jobs <= 0) return rc;
+    const int64_t* olo = reinterpret_cast<const int64_t*>(out_lo);
+    for (int64_t i = 0; i < n_jobs * n_keys; ++i) out_hi[i] = olo[i] >> 63;   // sign extension
+    if (rc == PE_OK && !wide_in) return PE_OK;
+    auto& jobs = ctx->aw_jobs;
+    jobs.clear();
+    for (int64_t j = 0; j < n_jobs; ++j)
+      if (out_overflow[j] || (wide_in && ctx->aw_mark[(size_t)j])) jobs.push_back(j);
+    ctx->err.clear();
+    if (agg_wide_pass(ctx, mode, n_keys, job_group_off, min_member, group_replicas, group_cont_off, cont_req_lo,
+                      cont_req_hi, cont_flags, jobs, out_lo, out_hi, out_overflow)) {
+      const void* o2 = std::memchr(out_overflow, 2, (size_t)n_jobs);
+      ctx->err = "128-bit overflow in job " + std::to_string(static_cast<const uint8_t*>(o2) - out_overflow);
+      return PE_EOVERFLOW;
+    }
+    return PE_OK;
+  });
 }
 
 // ------------------------------------------------------------------ fit mask

@@ -136,6 +136,14 @@ hipError_t launch_pg_min_resources(hipStream_t s, int mode, int64_t n_jobs, cons
                                    const int32_t* group_cont_off, const int64_t* cont_req,
                                    const uint8_t* cont_flags, int64_t* out_res, uint8_t* out_present,
                                    int32_t* out_members, uint8_t* out_overflow);
+// 128-bit aggregation of a compact CSR sub-batch (device-resident, offsets rebased to it), one lane per
+// (job, key) pair: requests req_hi * 2^64 + req_lo ([C][n_keys]; req_hi NULL = 0), results out_hi:out_lo
+// [n_jobs][n_keys] as signed 128-bit two's complement, out_flag [n_jobs][n_keys] = 1 where an
+// intermediate of the pair left [-2^127, 2^127) (its value is then 0).
+hipError_t launch_pg_agg_wide(hipStream_t s, int mode, int64_t n_jobs, int n_keys, const int32_t* job_group_off,
+                              const int32_t* min_member, const int32_t* group_replicas,
+                              const int32_t* group_cont_off, const uint64_t* req_lo, const uint64_t* req_hi,
+                              const uint32_t* cont_flags, uint64_t* out_lo, int64_t* out_hi, uint8_t* out_flag);
 
 // Device mask layout (tile-major, so every store writes whole 128-B lines): tiles of 16 jobs x 4
 // words (256 nodes); word (j, c) -- bit n%64 of chunk c = n/64 = fit(job j, local node n) -- sits at

@@ -290,6 +290,104 @@ hipError_t launch_pg_min_resources(hipStream_t s, int mode, int64_t n_jobs, cons
   return hipGetLastError();
 }
 
+// ---- 128-bit aggregation (pe_pg_min_resources_wide): agg_job_t restated step for step in 128 bits for
+// the rare jobs whose sums leave int64 (the reference's inf.Dec path).  Keys never interact, and 16
+// keys x 5 accumulators x 4 dwords would spill, so ONE LANE = ONE (job, key) PAIR: five 128-bit
+// accumulators (20 VGPRs) per lane, lanes of a job read neighbouring values of a container record.
+// A request is hi * 2^64 + lo < 2^127; pod-level sums are unsigned (overflow = a result >= 2^127), the
+// replica multiply is 128 x 31-bit magnitude from two 64 x 32 -> 96-bit products (v_mad_u64_u32 class),
+// then signed; the per-job sum is a signed 128-bit add.  Every step that leaves [-2^127, 2^127) sets the
+// pair's sticky flag and the pair answers 0.  Presence bits and members come from the int64 pass.
+using u128 = unsigned __int128;
+
+__device__ __forceinline__ u128 wide_add(u128 a, u128 b, bool* ovf) {   // a, b < 2^127: no wrap in 128 bits
+  const u128 r = a + b;
+  *ovf |= (uint64_t)(r >> 127) != 0;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void pg_agg_wide_kernel(
+    int mode, int64_t n_jobs, int n_keys, const int32_t* __restrict__ job_group_off,
+    const int32_t* __restrict__ min_member, const int32_t* __restrict__ group_replicas,
+    const int32_t* __restrict__ group_cont_off, const uint64_t* __restrict__ req_lo,
+    const uint64_t* __restrict__ req_hi, const uint32_t* __restrict__ cont_flags, uint64_t* __restrict__ out_lo,
+    int64_t* __restrict__ out_hi, uint8_t* __restrict__ out_flag) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_jobs * n_keys) return;
+  const int64_t j = t / n_keys;
+  const int d = (int)(t - j * n_keys);
+  const uint32_t bit = 1u << d;
+  const int32_t mm = mode == 1 ? min_member[j] : 0;
+  u128 acc = 0;   // two's complement
+  int32_t pod_cnt = 0;
+  bool ovf = false;
+  for (int32_t g = job_group_off[j]; g < job_group_off[j + 1]; ++g) {
+    const int32_t r = group_replicas[g];
+    int64_t k;
+    if (mode == 1) {
+      if (r <= 0) continue;
+      const int64_t room = (int64_t)mm - pod_cnt;
+      if (room <= 0) continue;
+      k = r < room ? r : room;
+      pod_cnt += (int32_t)k;
+    } else {
+      k = r;
+    }
+    u128 side = 0, initmax = 0, main_ = 0, over = 0;
+    bool pp = false;
+    for (int32_t c = group_cont_off[g]; c < group_cont_off[g + 1]; ++c) {
+      const uint32_t f = cont_flags[c];
+      const uint32_t kind = (f >> 16) & 3u;
+      if (mode == 1 && kind != 0) continue;
+      if (!(f & bit)) continue;
+      const int64_t i = (int64_t)c * n_keys + d;
+      const u128 v = ((u128)(req_hi ? req_hi[i] : 0) << 64) | req_lo[i];
+      pp = true;
+      if (kind == 0) main_ = wide_add(main_, v, &ovf);
+      else if (kind == 2) side = wide_add(side, v, &ovf);
+      else if (kind == 3) over = wide_add(over, v, &ovf);
+      else {
+        const u128 u = wide_add(side, v, &ovf);
+        initmax = u > initmax ? u : initmax;
+      }
+    }
+    if (!pp) continue;
+    u128 pod = wide_add(side, main_, &ovf);
+    pod = initmax > pod ? initmax : pod;
+    pod = wide_add(pod, over, &ovf);
+    // pod x |k|, |k| <= 2^31: 64 x 32-bit products of the two limbs, carried from lo to hi
+    const bool neg = k < 0;
+    const uint64_t m = (uint64_t)(neg ? -k : k);
+    const u128 p0 = (u128)(uint64_t)pod * m;
+    const u128 top = (u128)(uint64_t)(pod >> 64) * m + (uint64_t)(p0 >> 64);   // (< 2^96 + 2^32)
+    ovf |= (uint64_t)(top >> 64) != 0;
+    const u128 mag = (top << 64) | (uint64_t)p0;
+    const u128 lim = (u128)1 << 127;
+    ovf |= neg ? mag > lim : mag >= lim;   // (-2^127 is a value)
+    const u128 tv = neg ? (u128)0 - mag : mag;
+    const u128 s = acc + tv;
+    ovf |= (uint64_t)(((acc ^ s) & (tv ^ s)) >> 127) != 0;   // signed add left [-2^127, 2^127)
+    acc = s;
+  }
+  out_lo[t] = ovf ? 0 : (uint64_t)acc;
+  out_hi[t] = ovf ? 0 : (int64_t)(uint64_t)(acc >> 64);
+  out_flag[t] = ovf ? 1 : 0;
+}
+
+hipError_t launch_pg_agg_wide(hipStream_t s, int mode, int64_t n_jobs, int n_keys, const int32_t* job_group_off,
+                              const int32_t* min_member, const int32_t* group_replicas,
+                              const int32_t* group_cont_off, const uint64_t* req_lo, const uint64_t* req_hi,
+                              const uint32_t* cont_flags, uint64_t* out_lo, int64_t* out_hi, uint8_t* out_flag) {
+  if (n_jobs <= 0) return hipSuccess;
+  if (n_keys < 1 || n_keys > AGG_MAX_KEYS) return hipErrorInvalidValue;
+  const int64_t lanes = n_jobs * n_keys;
+  const int64_t blocks = (lanes + 255) / 256;
+  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pg_agg_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, s, mode, n_jobs, n_keys, job_group_off,
+                     min_member, group_replicas, group_cont_off, req_lo, req_hi, cont_flags, out_lo, out_hi, out_flag);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ fit mask (config 5)
 //
 // Wave tile = FM_CH chunks of 64 nodes held in VGPRs (4 dims x int64 + labels) x FM_JT jobs.

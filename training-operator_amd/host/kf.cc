@@ -176,6 +176,8 @@ struct AggOut {
   std::vector<std::string> keys;
   std::vector<int> scale;        // per key: results are counts of 10^scale
   std::vector<int64_t> res;      // [J][keys]
+  std::vector<int64_t> res_hi;   // [J][keys], wide only: the high limb (res is then the low limb's bits)
+  bool wide = false;             // pe_pg_min_resources_wide answered: overflow 1 = exact 128-bit value, 2 = none
   std::vector<uint8_t> present;  // [J][keys] 0 / 1
   std::vector<uint8_t> overflow;
   std::vector<int32_t> members;
@@ -184,7 +186,10 @@ struct AggOut {
 // One pe_pg_min_resources_keys call per slice of <= PE_MAX_KEYS keys (keys never interact; every
 // slice returns the same members).  A value with no int64 at its key's scale marks its job overflowed
 // on the host (its records carry 0), exactly like a sum the kernel flags.
-static AggOut run_agg(Engine& eng, int mode, const Flat& f) {
+// wide: through pe_pg_min_resources_wide instead -- such a value travels as two limbs (Scaled128), a
+// job whose sums leave int64 is summed by the 128-bit kernel (overflow 1, exact), and only a job with
+// no 128-bit answer, or a value of 2^127 and more, is flagged 2.
+static AggOut run_agg(Engine& eng, int mode, const Flat& f, bool wide = false) {
   const int64_t J = (int64_t)f.job_group_off.size() - 1;
   const int64_t C = (int64_t)f.cont_kind.size();
   const int nk = (int)f.keys.size();
@@ -192,44 +197,68 @@ static AggOut run_agg(Engine& eng, int mode, const Flat& f) {
   o.keys = f.keys;
   o.scale = f.Scales();
   o.res.assign((size_t)J * nk, 0);
+  o.wide = wide;
+  if (wide) o.res_hi.assign((size_t)J * nk, 0);
   o.present.assign((size_t)J * nk, 0);
   o.overflow.assign((size_t)J, 0);
   o.members.assign((size_t)J, 0);
   if (J == 0) return o;
-  std::vector<int64_t> val(f.ent_q.size(), 0);
+  std::vector<int64_t> val(f.ent_q.size(), 0), val_hi(wide ? f.ent_q.size() : 0, 0);
+  bool limbs = false;   // wide: some value needs the hi limb array
   for (int64_t j = 0; j < J; ++j)
     for (int32_t g = f.job_group_off[j]; g < f.job_group_off[j + 1]; ++g)
       for (int32_t c = f.group_cont_off[g]; c < f.group_cont_off[g + 1]; ++c)
         for (int32_t e = f.ent_off[c]; e < f.ent_off[c + 1]; ++e) {
+          if (wide) {
+            const std::optional<__int128> v = f.ent_q[e].Scaled128(o.scale[f.ent_key[e]]);
+            if (!v) {
+              o.overflow[j] = 2;
+              continue;
+            }
+            val[e] = (int64_t)(uint64_t)*v;
+            val_hi[e] = (int64_t)(uint64_t)((unsigned __int128)*v >> 64);
+            limbs |= val_hi[e] != 0 || val[e] < 0;
+            continue;
+          }
           const std::optional<int64_t> v = f.ent_q[e].Scaled(o.scale[f.ent_key[e]]);
           if (v) val[e] = *v;
           else o.overflow[j] = 1;
         }
-  std::vector<int64_t> req, res((size_t)J * PE_MAX_KEYS);
+  std::vector<int64_t> req, req_hi, res((size_t)J * PE_MAX_KEYS), res_hi(wide ? (size_t)J * PE_MAX_KEYS : 0);
   std::vector<uint32_t> flags((size_t)C);
   std::vector<uint16_t> pres((size_t)J);
   std::vector<uint8_t> ovf((size_t)J);
   for (int lo = 0; lo < std::max(nk, 1); lo += PE_MAX_KEYS) {
     const int n = std::max(1, std::min(PE_MAX_KEYS, nk - lo));   // (no key at all: one empty key for members)
     req.assign((size_t)C * n, 0);
+    if (limbs) req_hi.assign((size_t)C * n, 0);
     for (int64_t c = 0; c < C; ++c) {
       uint32_t fl = (uint32_t)f.cont_kind[c] << PE_KEYS_KIND_SHIFT;
       for (int32_t e = f.ent_off[c]; e < f.ent_off[c + 1]; ++e) {
         const int k = f.ent_key[e] - lo;
         if (k < 0 || k >= n || lo + k >= nk) continue;
         req[(size_t)c * n + k] = val[e];
+        if (limbs) req_hi[(size_t)c * n + k] = val_hi[e];
         fl |= 1u << k;
       }
       flags[c] = fl;
     }
-    const int rc = pe_pg_min_resources_keys(eng.ctx(), mode, J, n, f.job_group_off.data(), f.min_member.data(),
-                                            f.group_replicas.data(), f.group_cont_off.data(), req.data(),
-                                            flags.data(), res.data(), pres.data(), o.members.data(), ovf.data());
+    const int rc =
+        wide ? pe_pg_min_resources_wide(eng.ctx(), mode, J, n, f.job_group_off.data(), f.min_member.data(),
+                                        f.group_replicas.data(), f.group_cont_off.data(),
+                                        reinterpret_cast<const uint64_t*>(req.data()),
+                                        limbs ? reinterpret_cast<const uint64_t*>(req_hi.data()) : nullptr,
+                                        flags.data(), reinterpret_cast<uint64_t*>(res.data()), res_hi.data(),
+                                        pres.data(), o.members.data(), ovf.data())
+             : pe_pg_min_resources_keys(eng.ctx(), mode, J, n, f.job_group_off.data(), f.min_member.data(),
+                                        f.group_replicas.data(), f.group_cont_off.data(), req.data(), flags.data(),
+                                        res.data(), pres.data(), o.members.data(), ovf.data());
     if (rc != PE_OK && rc != PE_EOVERFLOW) throw Error{rc, pe_last_error(eng.ctx())};
     for (int64_t j = 0; j < J; ++j) {
-      o.overflow[j] |= ovf[j];
+      o.overflow[j] = wide ? std::max(o.overflow[j], ovf[j]) : (uint8_t)(o.overflow[j] | ovf[j]);
       for (int k = 0; k < n && lo + k < nk; ++k) {
         o.res[(size_t)j * nk + lo + k] = res[(size_t)j * n + k];
+        if (wide) o.res_hi[(size_t)j * nk + lo + k] = res_hi[(size_t)j * n + k];
         o.present[(size_t)j * nk + lo + k] = (uint8_t)(pres[j] >> k & 1);
       }
     }
@@ -238,7 +267,8 @@ static AggOut run_agg(Engine& eng, int mode, const Flat& f) {
 }
 
 static ResourceList to_list(const AggOut& o, int64_t j, const std::map<std::string, Format>* formats = nullptr) {
-  if (o.overflow[j]) throw Error{PE_EOVERFLOW, "int64 overflow: the reference would switch to inf.Dec"};
+  if (o.wide && o.overflow[j] == 2) throw Error{PE_EOVERFLOW, "a sum or a value has no signed 128-bit integer at its key's scale"};
+  if (!o.wide && o.overflow[j]) throw Error{PE_EOVERFLOW, "int64 overflow: the reference would switch to inf.Dec"};
   ResourceList rl;
   const size_t nk = o.keys.size();
   for (size_t k = 0; k < nk; ++k) {
@@ -246,7 +276,12 @@ static ResourceList to_list(const AggOut& o, int64_t j, const std::map<std::stri
     const std::string& key = o.keys[k];
     const auto f = formats ? formats->find(key) : std::map<std::string, Format>::const_iterator{};
     const Format fmt = formats && f != formats->end() ? f->second : key == "cpu" ? Format::kDecimalSI : Format::kBinarySI;
-    rl[key] = Quantity::FromScaled(o.res[j * nk + k], o.scale[k], fmt);
+    if (o.wide) {
+      const unsigned __int128 v = (unsigned __int128)(uint64_t)o.res_hi[j * nk + k] << 64 | (uint64_t)o.res[j * nk + k];
+      rl[key] = Quantity::FromScaled128((__int128)v, o.scale[k], fmt);
+    } else {
+      rl[key] = Quantity::FromScaled(o.res[j * nk + k], o.scale[k], fmt);
+    }
   }
   return rl;
 }
@@ -309,11 +344,33 @@ ResourceList CalcPGMinResources(Engine& eng, int32_t minMember, const std::map<R
   return to_list(run_agg(eng, PE_MODE_V1, f), 0, &formats);
 }
 
+ResourceList CalcPGMinResourcesWide(Engine& eng, int32_t minMember, const std::map<ReplicaType, ReplicaSpec>& replicas,
+                                    const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order) {
+  Flat f;
+  FlattenV1Job(minMember, replicas, pcGetFunc, &f, order);
+  const auto formats = MinResourcesFormatsV1(minMember, replicas, pcGetFunc, order);
+  return to_list(run_agg(eng, PE_MODE_V1, f, true), 0, &formats);
+}
+
+static std::vector<ResourceList> calc_batch(Engine& eng, const std::vector<V1Job>& jobs,
+                                            const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order, bool wide);
+
 std::vector<ResourceList> CalcPGMinResourcesBatch(Engine& eng, const std::vector<V1Job>& jobs,
                                                   const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order) {
+  return calc_batch(eng, jobs, pcGetFunc, order, false);
+}
+
+std::vector<ResourceList> CalcPGMinResourcesBatchWide(Engine& eng, const std::vector<V1Job>& jobs,
+                                                      const PriorityClassGetFunc& pcGetFunc,
+                                                      const V1OrderPolicy& order) {
+  return calc_batch(eng, jobs, pcGetFunc, order, true);
+}
+
+static std::vector<ResourceList> calc_batch(Engine& eng, const std::vector<V1Job>& jobs,
+                                            const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order, bool wide) {
   Flat f;
   for (const V1Job& j : jobs) FlattenV1Job(j.min_member, j.replicas, pcGetFunc, &f, order);
-  AggOut o = run_agg(eng, PE_MODE_V1, f);
+  AggOut o = run_agg(eng, PE_MODE_V1, f, wide);
   std::vector<ResourceList> out;
   for (size_t j = 0; j < jobs.size(); ++j) {
     const auto formats = MinResourcesFormatsV1(jobs[j].min_member, jobs[j].replicas, pcGetFunc, order);
@@ -432,6 +489,23 @@ bool NeedsCreateOrUpdate(const PodGroup* old, const PodGroup& pg, bool suspended
 std::vector<CoScheduling::BuildResult> CoScheduling::BuildBatch(const std::vector<const Info*>& infos,
                                                                 const std::vector<const TrainJob*>& trainJobs,
                                                                 const std::vector<const PodGroup*>& existing) {
+  return BuildBatchImpl(infos, trainJobs, existing, false);
+}
+
+std::vector<CoScheduling::BuildResult> CoScheduling::BuildBatchWide(const std::vector<const Info*>& infos,
+                                                                    const std::vector<const TrainJob*>& trainJobs,
+                                                                    const std::vector<const PodGroup*>& existing) {
+  return BuildBatchImpl(infos, trainJobs, existing, true);
+}
+
+CoScheduling::BuildResult CoScheduling::BuildWide(const Info* info, const TrainJob* trainJob, const PodGroup* existing) {
+  return BuildBatchImpl({info}, {trainJob}, {existing}, true)[0];
+}
+
+std::vector<CoScheduling::BuildResult> CoScheduling::BuildBatchImpl(const std::vector<const Info*>& infos,
+                                                                    const std::vector<const TrainJob*>& trainJobs,
+                                                                    const std::vector<const PodGroup*>& existing,
+                                                                    bool wide) {
   std::vector<BuildResult> out(infos.size());
   std::vector<size_t> idx;
   Flat f;
@@ -449,7 +523,7 @@ std::vector<CoScheduling::BuildResult> CoScheduling::BuildBatch(const std::vecto
   }
   AggOut o;
   try {
-    o = run_agg(eng_, PE_MODE_V2, f);
+    o = run_agg(eng_, PE_MODE_V2, f, wide);
   } catch (const Error& e) {
     for (size_t k : idx) out[k].error = e;
     return out;

@@ -201,6 +201,13 @@ int32_t GetTotalReplicas(const std::map<ReplicaType, ReplicaSpec>& replicas);
 ResourceList CalcPGMinResources(Engine& eng, int32_t minMember, const std::map<ReplicaType, ReplicaSpec>& replicas,
                                 const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order = {});
 
+// The same with an exact answer past int64 (pe_pg_min_resources_wide): a value with no int64 at its
+// key's scale travels as two limbs and a sum that leaves int64 is the engine's exact 128-bit one, so
+// the list is what the reference holds in inf.Dec.  Throws {PE_EOVERFLOW} only when a sum or a value
+// has no signed 128-bit integer at its key's scale.
+ResourceList CalcPGMinResourcesWide(Engine& eng, int32_t minMember, const std::map<ReplicaType, ReplicaSpec>& replicas,
+                                    const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order = {});
+
 struct V1Job {
   int32_t min_member;
   std::map<ReplicaType, ReplicaSpec> replicas;
@@ -208,6 +215,10 @@ struct V1Job {
 // One kernel launch for a batch of jobs (the throughput form of the same rule).
 std::vector<ResourceList> CalcPGMinResourcesBatch(Engine& eng, const std::vector<V1Job>& jobs,
                                                   const PriorityClassGetFunc& pcGetFunc, const V1OrderPolicy& order = {});
+
+std::vector<ResourceList> CalcPGMinResourcesBatchWide(Engine& eng, const std::vector<V1Job>& jobs,
+                                                      const PriorityClassGetFunc& pcGetFunc,
+                                                      const V1OrderPolicy& order = {});
 
 // job.go:250-277: minMember = MinAvailable ?? GetTotalReplicas; MinResources verbatim if set.
 struct PodGroupSpecV1 {
@@ -329,8 +340,17 @@ class CoScheduling : public Plugin {
   std::vector<BuildResult> BuildBatch(const std::vector<const Info*>& infos,
                                       const std::vector<const TrainJob*>& trainJobs,
                                       const std::vector<const PodGroup*>& existing);
+  // Build / BuildBatch through pe_pg_min_resources_wide: MinResources exact past int64; the error is
+  // {PE_EOVERFLOW} only for a sum with no signed 128-bit integer at its key's scale.
+  BuildResult BuildWide(const Info* info, const TrainJob* trainJob, const PodGroup* existing);
+  std::vector<BuildResult> BuildBatchWide(const std::vector<const Info*>& infos,
+                                          const std::vector<const TrainJob*>& trainJobs,
+                                          const std::vector<const PodGroup*>& existing);
 
  private:
+  std::vector<BuildResult> BuildBatchImpl(const std::vector<const Info*>& infos,
+                                          const std::vector<const TrainJob*>& trainJobs,
+                                          const std::vector<const PodGroup*>& existing, bool wide);
   Engine& eng_;
 };
 

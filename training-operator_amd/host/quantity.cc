@@ -172,6 +172,45 @@ std::optional<int64_t> Quantity::Scaled(int s) const {
   return (int64_t)x;
 }
 
+std::optional<__int128> Quantity::Scaled128(int s) const {
+  if (mant_ < 0) return std::nullopt;
+  if (mant_ == 0) return (__int128)0;
+  if (s > Exp10()) return std::nullopt;   // (not an integer count of 10^s)
+  constexpr unsigned __int128 kTop = (unsigned __int128)1 << 127;
+  unsigned __int128 x = (unsigned __int128)mant_;
+  int k = e10_ - s;                       // value / 10^s = mant * 2^e2 * 10^k
+  while (k < 0 && x % 10 == 0) {          // the exact divisions first: x never grows past the result
+    x /= 10;
+    ++k;
+  }
+  for (int i = 0; i < e2_; ++i) {
+    if (k < 0 && x % 5 == 0) {            // a 2 of 2^e2 pairs with a 5 left in x: x 2 / 10, never larger
+      x /= 5;
+      ++k;
+      continue;
+    }
+    if (x >= kTop / 2) return std::nullopt;
+    x *= 2;
+  }
+  while (k < 0) {
+    x /= 10;
+    ++k;
+  }
+  for (; k > 0; --k) {
+    if (x > (kTop - 1) / 10) return std::nullopt;
+    x *= 10;
+  }
+  return (__int128)x;
+}
+
+Quantity Quantity::FromScaled128(__int128 v, int s, Format f) {
+  Quantity q;
+  q.mant_ = v;
+  q.e10_ = s;
+  q.format_ = f;
+  return q;
+}
+
 Quantity Quantity::FromScaled(int64_t v, int s, Format f) {
   Quantity q;
   q.mant_ = v;

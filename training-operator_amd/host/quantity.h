@@ -38,6 +38,11 @@ class Quantity {
   int Exp10() const;
   std::optional<int64_t> Scaled(int s) const;
   static Quantity FromScaled(int64_t v, int s, Format f);
+  // The same past int64 (placement.h pe_pg_min_resources_wide): Scaled128(s) is value / 10^s as an exact
+  // integer in [0, 2^127) (s <= Exp10()); nullopt only for a negative value, one that is no integer
+  // count of 10^s, or one of 2^127 and more.  FromScaled128: any signed 128-bit count of 10^s.
+  std::optional<__int128> Scaled128(int s) const;
+  static Quantity FromScaled128(__int128 v, int s, Format f);
   Quantity WithFormat(Format f) const {
     Quantity q = *this;
     q.format_ = f;

@@ -23,7 +23,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
-           "PE_NODE_SET", "PE_NODE_REMOVE"]
+           "PE_NODE_SET", "PE_NODE_REMOVE", "wide_ints", "wide_limbs"]
 
 
 class PlacementError(RuntimeError):
@@ -38,6 +38,35 @@ def _p(a: Optional[np.ndarray]):
 
 def _c(a, dt) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dt)
+
+
+def wide_ints(lo, hi) -> np.ndarray:
+    """The signed 128-bit values hi * 2^64 + lo of pg_min_resources_wide's (lo u64, hi i64) limb arrays
+    as Python ints (an object array of the same shape)."""
+    lo = np.asarray(lo, dtype=np.uint64)
+    hi = np.asarray(hi, dtype=np.int64)
+    out = np.empty(lo.shape, dtype=object)
+    flat = out.reshape(-1)
+    for i, (a, b) in enumerate(zip(lo.reshape(-1).tolist(), hi.reshape(-1).tolist())):
+        flat[i] = (b << 64) + a
+    return out
+
+
+def wide_limbs(values):
+    """Non-negative Python ints below 2^128 (any nesting / object array) -> (lo, hi) uint64 limb arrays,
+    the request form of pg_min_resources_wide's cont_req_lo / cont_req_hi (the engine takes values
+    below 2^127)."""
+    v = np.asarray(values, dtype=object)
+    lo = np.zeros(v.shape, dtype=np.uint64)
+    hi = np.zeros(v.shape, dtype=np.uint64)
+    fl, fh = lo.reshape(-1), hi.reshape(-1)
+    for i, x in enumerate(v.reshape(-1).tolist()):
+        x = int(x)
+        if not 0 <= x < 1 << 128:
+            raise ValueError(f"{x} has no two-limb form")
+        fl[i] = x & (2**64 - 1)
+        fh[i] = x >> 64
+    return lo, hi
 
 
 def comm_id() -> bytes:
@@ -235,6 +264,40 @@ class Engine:
                                                _p(out), _p(pres), _p(mem), _p(ovf))
         self._chk(rc, "pe_pg_min_resources_keys", ok=(0, _abi.PE_EOVERFLOW) if allow_overflow else (0,))
         return out, pres, mem, ovf
+
+    def pg_min_resources_wide(self, mode, job_group_off, min_member, group_replicas, group_cont_off, cont_req_lo,
+                              cont_flags, cont_req_hi=None, allow_overflow=True):
+        """pe_pg_min_resources_wide: the key-table aggregation with exact answers past int64.  A request
+        is cont_req_hi * 2^64 + cont_req_lo ([C][n_keys]; without cont_req_hi the low limbs are int64
+        values, as in pg_min_resources_keys).  Returns (lo [J][n_keys] u64, hi [J][n_keys] i64, present
+        [J] u16, members, overflow): the signed 128-bit sums hi:lo (wide_ints), overflow 0 = the int64 path
+        answered, 1 = exact 128-bit value, 2 = left 128 bits (values 0; the call's code is PE_EOVERFLOW)."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        mm = None if min_member is None else _c(min_member, np.int32)
+        rep = _c(group_replicas, np.int32)
+        gco = _c(group_cont_off, np.int32)
+        if cont_req_hi is None:
+            lo = np.ascontiguousarray(cont_req_lo, dtype=np.int64)
+            hi = None
+        else:
+            lo = np.ascontiguousarray(cont_req_lo, dtype=np.uint64)
+            hi = np.ascontiguousarray(cont_req_hi, dtype=np.uint64)
+            if hi.shape != lo.shape:
+                raise ValueError("cont_req_hi must have cont_req_lo's shape")
+        if lo.ndim != 2:
+            raise ValueError("cont_req_lo must be [C][n_keys]")
+        nk = lo.shape[1]
+        fl = _c(cont_flags, np.uint32)
+        out_lo = np.zeros((J, nk), dtype=np.uint64)
+        out_hi = np.zeros((J, nk), dtype=np.int64)
+        pres = np.zeros(J, dtype=np.uint16)
+        mem = np.zeros(J, dtype=np.int32)
+        ovf = np.zeros(J, dtype=np.uint8)
+        rc = self.lib.pe_pg_min_resources_wide(self.h, mode, J, nk, _p(jgo), _p(mm), _p(rep), _p(gco), _p(lo), _p(hi),
+                                               _p(fl), _p(out_lo), _p(out_hi), _p(pres), _p(mem), _p(ovf))
+        self._chk(rc, "pe_pg_min_resources_wide", ok=(0, _abi.PE_EOVERFLOW) if allow_overflow else (0,))
+        return out_lo, out_hi, pres, mem, ovf
 
     # ------------------------------------------------------------ fit mask
     def jobs_upload(self, req, need=None):

@@ -52,7 +52,7 @@ class PeStats(ctypes.Structure):
                 ("xchg_zc_windows", ctypes.c_int64), ("xchg_wait_ms", ctypes.c_double),
                 ("xchg_merge_ms", ctypes.c_double),
                 ("agg_segments", ctypes.c_int64), ("agg_narrow_segments", ctypes.c_int64),
-                ("agg_wire_bytes", ctypes.c_int64)]
+                ("agg_wire_bytes", ctypes.c_int64), ("agg_wide_jobs", ctypes.c_int64)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -76,6 +76,7 @@ SIGNATURES = {
     "pe_read_residuals": (ctypes.c_int, [P, P]),
     "pe_pg_min_resources": (ctypes.c_int, [P, i32, i64, P, P, P, P, P, P, P, P, P, P]),
     "pe_pg_min_resources_keys": (ctypes.c_int, [P, i32, i64, i32, P, P, P, P, P, P, P, P, P, P]),
+    "pe_pg_min_resources_wide": (ctypes.c_int, [P, i32, i64, i32, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pe_fit_mask": (ctypes.c_int, [P, i64, P, P, P, ctypes.POINTER(P), ctypes.POINTER(i64)]),
     "pe_jobs_upload": (ctypes.c_int, [P, i64, P, P]),
     "pe_fit_mask_run": (ctypes.c_int, [P]),
