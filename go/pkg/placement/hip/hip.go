@@ -58,6 +58,8 @@ const (
 	// need carries NeedIsland is placed as one unit on one island node (placement.h).
 	LabelIsland = uint32(C.PE_LABEL_ISLAND)
 	NeedIsland  = uint32(C.PE_NEED_ISLAND)
+	// CapMax is where GangCapacity's per-node capacity saturates.
+	CapMax = int32(C.PE_CAP_MAX)
 )
 
 // Node inventory update ops.
@@ -587,6 +589,24 @@ func (e *Engine) FitMaskRowPitch() (int64, error) {
 	var w C.int64_t
 	rc := C.pe_fit_mask_row_pitch(e.ctx, &w)
 	return int64(w), e.err(rc, "pe_fit_mask_row_pitch")
+}
+
+// GangCapacity answers, per job shape (req [J][4], need [J] or nil) and against the shard's current
+// residuals, how many pods of that shape fit: slots = the sum over the nodes (a gang of identical pods
+// fits iff its size <= slots), maxNode = the largest single node (an island gang, NeedIsland in need,
+// fits iff its size <= maxNode), nodes = the nodes holding at least one (FitMask's count).  Read-only:
+// residuals and the staged fit batch stay as they are.  Sharded: add slots and nodes over the shards,
+// take the maximum of maxNode.
+func (e *Engine) GangCapacity(req []int64, need []uint32) (slots []int64, maxNode []int32, nodes []int64, err error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, nil, nil, fmt.Errorf("GangCapacity: %d needs for %d jobs", len(need), J)
+	}
+	slots = make([]int64, J)
+	maxNode = make([]int32, J)
+	nodes = make([]int64, J)
+	rc := C.pe_gang_capacity(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr64(slots), ptr32(maxNode), ptr64(nodes))
+	return slots, maxNode, nodes, e.err(rc, "pe_gang_capacity")
 }
 
 // Gangs is a greedy placement batch: jobs of groups of identical pods (include/placement.h).

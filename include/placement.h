@@ -305,6 +305,32 @@ int pe_fit_mask_layout(const pe_ctx* ctx, int32_t* layout);
  * the other layouts). */
 int pe_fit_mask_row_pitch(const pe_ctx* ctx, int64_t* words);
 
+/* (ABI 7, additive) Gang capacity: how many pods of job j's shape the shard holds right now -- the
+ * read-only what-if of a gang, where the fit mask answers for one pod.  NO reference function: the
+ * consumers are the gang schedulers that read the PodGroup the operator writes (scheduler-plugins
+ * coscheduling PreFilter, Volcano enqueue; pkg/controller.v1/control/podgroup_control.go:36-54), which
+ * compare MinResources with what the cluster has free before they place anything.  The rule is
+ * SURVEY.md Appendix B's: one pod of shape q on node n lowers floor(res_d / q_d) by exactly one in
+ * every dimension with q_d > 0.  With fit(j, n) as pe_fit_mask defines it, against the CURRENT
+ * residuals of this shard:
+ *   cap(j, n) = 0                                                              if !fit(j, n)
+ *             = min(PE_CAP_MAX, min over d with req_d > 0 of floor(res_d / req_d))   otherwise
+ *               (no d with req_d > 0: PE_CAP_MAX)
+ *   out_slots[j]    = sum over n of cap(j, n)   a gang of identical pods fits iff its size <= out_slots
+ *   out_max_node[j] = max over n of cap(j, n)   (0 on an empty shard) an island gang -- PE_NEED_ISLAND in
+ *                                               need[j], matched like any label bit -- fits iff its size
+ *                                               <= out_max_node
+ *   out_nodes[j]    = nodes with cap(j, n) >= 1 = pe_fit_mask's count for the same row
+ * Exact: integer division of the int64 residuals, no rounding.  Per shard, as pe_fit_mask's counts:
+ * the caller adds out_slots and out_nodes over shards and takes the maximum of out_max_node.  A job
+ * of several groups needs every group's capacity, which is necessary, not sufficient: its exact
+ * answer is pe_place_greedy.  Residuals and the staged fit-mask state (pe_jobs_upload ...
+ * pe_fit_mask_rows) are left as they are.  Each out_* may be NULL; need NULL = 0.  A negative request
+ * is PE_EINVAL (the first offending index in pe_last_error), a call before pe_load_nodes PE_ESTATE. */
+#define PE_CAP_MAX 2147483647 /* per-node capacity saturates here: the largest group_count */
+int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, const uint32_t* need /* or NULL = 0 */,
+                     int64_t* out_slots, int32_t* out_max_node, int64_t* out_nodes);
+
 /* Greedy best-fit all-or-nothing gang placement.  Jobs in (priority
  * desc, index asc) order, groups of a job in the given order, pods of a group identical.
  *   job_group_off[J+1], priority[J], group_count[G] (pods to place), group_req[G][4],

@@ -30,6 +30,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pe_divmagic.h"
 #include "pe_hostx.h"
 #include "pe_kernels.h"
 #include "pe_merge.h"
@@ -415,6 +416,16 @@ struct pe_ctx {
   DevBuf<uint8_t> aw_dev;
   std::vector<int64_t> aw_jobs, aw_lo;
   std::vector<uint8_t> aw_mark;
+  // gang capacity (pe_gang_capacity): the call's distinct shapes and their results (pinned), the device
+  // copies, the per-node-block partials, the dedupe table and each job's shape.  Grow and are reused;
+  // nothing of the staged fit mask is shared.
+  HostBuf<pe::CapShape> cp_hshapes;
+  HostBuf<pe::CapAcc> cp_hout;
+  DevBuf<pe::CapShape> cp_shapes;
+  DevBuf<pe::CapAcc> cp_part, cp_out;
+  std::vector<pe::CapShape> cp_uniq;
+  std::vector<int32_t> cp_tab, cp_of;
+  hipEvent_t cp_ev[2] = {nullptr, nullptr};   // PE_CAP_EVENTS=1: around the call's kernels
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -485,6 +496,9 @@ struct pe_ctx {
     a_jgo.release(); a_mm.release(); a_rep.release(); a_gco.release(); a_mem.release();
     a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
     aw_stage.release(); aw_outh.release(); aw_dev.release();
+    cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
+    for (hipEvent_t e : cp_ev)
+      if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
     g_upd.release(); g_kn.release(); g_lo.release(); h_groups.release(); h_groups2.release(); h_out.release(); h_out2.release(); h_own.release(); h_merged.release(); h_upd.release();
     for (auto& x : h_xg) x.release();
@@ -2649,6 +2663,110 @@ int pe_fit_mask(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t*
     else hipchk(hipStreamSynchronize(ctx->stream), "sync fit");
     if (dev_mask) *dev_mask = ctx->mask.p;
     if (words_per_row) *words_per_row = ctx->Wn;
+    return PE_OK;
+  });
+}
+
+// Gang capacity: the distinct (request, need) shapes of the batch go to the device with the
+// reciprocals of their requests (pe_divmagic.h), gang_capacity_kernel answers per shape over the
+// shard's current residuals, and the host scatters the answers back to the jobs.  Own buffers: the
+// staged fit-mask state is not touched.  PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity_latency.py):
+// hipEvents around the kernels; a successful call then leaves "S=<shapes> kernels_ms=<time>" in
+// pe_last_error.
+int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, int64_t* out_slots,
+                     int32_t* out_max_node, int64_t* out_nodes) {
+  return guarded(ctx, [&]() -> int {
+    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
+    if (n_jobs == 0) return PE_OK;
+    if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
+    need_ptr(req, "req");
+    check_req(req, n_jobs, "req");
+    // distinct shapes, in first-seen order (open addressing; a job equal to its predecessor skips the probe)
+    auto& uniq = ctx->cp_uniq;
+    auto& of = ctx->cp_of;
+    auto& tab = ctx->cp_tab;
+    uniq.clear();
+    of.resize((size_t)n_jobs);
+    size_t cap = 16;
+    while (cap < (size_t)n_jobs * 2) cap <<= 1;
+    tab.assign(cap, -1);
+    auto same = [&](const pe::CapShape& s, const int64_t* q, uint32_t nd) {
+      return s.q[0] == q[0] && s.q[1] == q[1] && s.q[2] == q[2] && s.q[3] == q[3] && s.need == nd;
+    };
+    for (int64_t j = 0; j < n_jobs; ++j) {
+      const int64_t* q = req + j * pe::D;
+      const uint32_t nd = need ? need[j] : 0u;
+      if (j > 0 && same(uniq[(size_t)of[(size_t)j - 1]], q, nd)) {
+        of[(size_t)j] = of[(size_t)j - 1];
+        continue;
+      }
+      uint64_t h = nd;
+      for (int d = 0; d < pe::D; ++d) {
+        h = (h ^ (uint64_t)q[d]) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+      }
+      size_t at = (size_t)h & (cap - 1);
+      while (tab[at] >= 0 && !same(uniq[(size_t)tab[at]], q, nd)) at = (at + 1) & (cap - 1);
+      if (tab[at] < 0) {
+        tab[at] = (int32_t)uniq.size();
+        pe::CapShape sp{};
+        for (int d = 0; d < pe::D; ++d) {
+          sp.q[d] = q[d];
+          if (q[d] > 0) {
+            const pe::DivMagic dm = pe::div_magic((uint64_t)q[d]);
+            sp.m[d] = dm.m;
+            sp.sh[d] = dm.shift;
+          }
+        }
+        sp.need = nd;
+        uniq.push_back(sp);
+      }
+      of[(size_t)j] = tab[at];
+    }
+    const int64_t S = (int64_t)uniq.size();
+    const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
+    float kernel_ms = 0.f;
+    hipchk(ctx->cp_hout.ensure((size_t)S), "alloc pinned capacity results");
+    if (ctx->Ns == 0) {   // an empty shard holds nothing
+      std::memset((void*)ctx->cp_hout.p, 0, (size_t)S * sizeof(pe::CapAcc));
+    } else {
+      hipchk(ctx->cp_hshapes.ensure((size_t)S), "alloc pinned shapes");
+      hipchk(ctx->cp_shapes.ensure((size_t)S), "alloc shapes");
+      hipchk(ctx->cp_out.ensure((size_t)S), "alloc capacity results");
+      std::memcpy((void*)ctx->cp_hshapes.p, uniq.data(), (size_t)S * sizeof(pe::CapShape));
+      // shapes per launch: the partials (one record per node block and shape) stay within 64 MiB
+      const int64_t gx = pe::cap_node_blocks(ctx->Ns);
+      const int64_t fit64 = (int64_t(4) << 20) / gx / pe::CP_TS * pe::CP_TS;
+      const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(pe::CP_TS, fit64));
+      hipchk(ctx->cp_part.ensure((size_t)(gx * chunk)), "alloc capacity partials");
+      hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)S * sizeof(pe::CapShape), hipMemcpyHostToDevice,
+                            ctx->stream),
+             "H2D shapes");
+      if (events) {
+        for (hipEvent_t& e : ctx->cp_ev)
+          if (!e) hipchk(hipEventCreate(&e), "event create");
+        hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
+      }
+      for (int64_t s0 = 0; s0 < S; s0 += chunk)
+        hipchk(pe::launch_gang_capacity(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->Ns, ctx->cp_shapes.p + s0,
+                                        std::min(chunk, S - s0), ctx->cp_part.p, ctx->cp_out.p + s0),
+               "launch gang_capacity");
+      if (events) hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
+      hipchk(hipMemcpyAsync(ctx->cp_hout.p, ctx->cp_out.p, (size_t)S * sizeof(pe::CapAcc), hipMemcpyDeviceToHost,
+                            ctx->stream),
+             "D2H capacity results");
+      hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity");
+      if (events) hipchk(hipEventElapsedTime(&kernel_ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
+    }
+    const pe::CapAcc* a = ctx->cp_hout.p;
+    for (int64_t j = 0; j < n_jobs; ++j) {
+      const pe::CapAcc& r = a[of[(size_t)j]];
+      if (out_slots) out_slots[j] = (int64_t)r.slots;
+      if (out_max_node) out_max_node[j] = (int32_t)r.max_node;
+      if (out_nodes) out_nodes[j] = (int64_t)r.nodes;
+    }
+    if (events) ctx->err = "S=" + std::to_string(S) + " kernels_ms=" + std::to_string(kernel_ms);
     return PE_OK;
   });
 }

@@ -438,4 +438,32 @@ static_assert(sizeof(NodeUpd) == 48, "NodeUpd must be 48 B");
 hipError_t launch_scatter_nodes(hipStream_t s, int64_t* res, int64_t* res0, int64_t stride, uint32_t* labels,
                                 int32_t* island, const NodeUpd* upd, int64_t n);
 
+// ---- gang capacity (pe_gang_capacity, pe_capacity.hip)
+constexpr int CP_THREADS = 256;                  // threads per block
+constexpr int CP_NPT = 4;                        // nodes per thread, kept in registers
+constexpr int CP_SPAN = CP_THREADS * CP_NPT;     // nodes per block
+constexpr int CP_TS = 64;                        // shapes between two block folds
+constexpr uint64_t CP_CAP_MAX = 2147483647;      // PE_CAP_MAX
+__host__ __device__ inline int64_t cap_node_blocks(int64_t Ns) { return (Ns + CP_SPAN - 1) / CP_SPAN; }
+// One distinct pod shape: the request, the label need and per dimension with q > 0 the reciprocal of
+// the request (pe_divmagic.h div_magic; unused where q == 0).  96 B, read through a uniform address.
+struct alignas(32) CapShape {
+  int64_t q[D];
+  uint64_t m[D];
+  uint32_t sh[D];
+  uint32_t need;
+  uint32_t pad_[3];
+};
+static_assert(sizeof(CapShape) == 96, "CapShape must be 96 B");
+// A shape's result over a set of nodes: sum of the capacities, the largest one, nodes with capacity >= 1.
+struct CapAcc {
+  uint64_t slots;
+  uint32_t max_node;
+  uint32_t nodes;
+};
+static_assert(sizeof(CapAcc) == 16, "CapAcc must be 16 B");
+// out[s] (s < S) over the shard's Ns nodes; partials: cap_node_blocks(Ns) * S records of scratch.
+hipError_t launch_gang_capacity(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
+                                const CapShape* shapes, int64_t S, CapAcc* partials, CapAcc* out);
+
 }  // namespace pe

@@ -16,14 +16,14 @@ from typing import Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
 
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
-           "PE_NODE_SET", "PE_NODE_REMOVE", "wide_ints", "wide_limbs"]
+           "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs"]
 
 
 class PlacementError(RuntimeError):
@@ -341,6 +341,24 @@ class Engine:
         out = np.zeros((n_rows, w), dtype=np.uint64)
         self._chk(self.lib.pe_fit_mask_rows(self.h, row0, n_rows, _p(out)), "pe_fit_mask_rows")
         return out
+
+    # ------------------------------------------------------------ gang capacity
+    def gang_capacity(self, req, need=None):
+        """pe_gang_capacity: per job shape (req [J][4], need [J] or None) how many pods of that shape this
+        shard's current residuals hold.  Returns (slots int64[J], max_node int32[J], nodes int64[J]): the
+        sum over the nodes, the largest single node (saturating at PE_CAP_MAX) and the nodes holding at
+        least one.  Read-only: residuals and the staged fit batch are untouched."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        slots = np.zeros(J, dtype=np.int64)
+        max_node = np.zeros(J, dtype=np.int32)
+        nodes = np.zeros(J, dtype=np.int64)
+        self._chk(self.lib.pe_gang_capacity(self.h, J, _p(req), _p(nd), _p(slots), _p(max_node), _p(nodes)),
+                  "pe_gang_capacity")
+        return slots, max_node, nodes
 
     # ------------------------------------------------------------ greedy
     def place_greedy(self, job_group_off, priority, group_count, group_req, group_need=None):
