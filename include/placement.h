@@ -294,7 +294,12 @@ int pe_pg_min_resources_wide(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t 
  * One-shot form: upload + compute + counts to host; *dev_mask receives the device pointer. */
 int pe_fit_mask(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, const uint32_t* need,
                 int64_t* out_feasible_count, const uint64_t** dev_mask, int64_t* words_per_row);
-/* Staged form (device-resident inputs, used by the benchmark): */
+/* Staged form (device-resident inputs, used by the benchmark).  pe_jobs_upload (and pe_fit_mask)
+ * plans the batch for the shard loaded at that moment; every pe_fit_mask_run re-reads the CURRENT
+ * residuals and labels, so pe_update_nodes, pe_reset_residuals, pe_place_greedy and pe_gang_capacity
+ * keep the staged batch valid and the next run sees their effect.  pe_load_nodes invalidates it:
+ * after a load, pe_fit_mask_run, pe_fit_counts and pe_fit_mask_rows return PE_ESTATE until the next
+ * pe_jobs_upload or pe_fit_mask. */
 int pe_jobs_upload(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need);
 int pe_fit_mask_run(pe_ctx* ctx); /* asynchronous on the context stream */
 int pe_fit_counts(pe_ctx* ctx, int64_t* out_feasible_count); /* synchronizes */

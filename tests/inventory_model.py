@@ -1,0 +1,112 @@
+"""Host model of one engine context's inventory: numpy plus the C oracle, no engine.
+
+The model follows include/placement.h: residual = cap - used; pe_update_nodes takes the last entry
+per slot (SET: residual, labels and island replaced, also in the reset snapshot; REMOVE: the slot
+never fits, labels 0, also in the snapshot); pe_reset_residuals goes back to the snapshot (labels
+are not part of it); pe_place_greedy lowers the residuals by what it places.  Labels are kept as the
+engine keeps them: bit 31 = the node has an island (synth.island_labels)."""
+import numpy as np
+
+import oracle
+from placement import PE_NODE_REMOVE, PE_NODE_SET, synth
+
+NEVER = np.iinfo(np.int64).min
+
+
+def make_deltas(n_nodes, n_upd, seed):
+    """Random SET/REMOVE batch with repeated slots (SET -> REMOVE -> SET chains)."""
+    rng = np.random.default_rng(seed)
+    donor = synth.make_inventory(n_upd, seed + 1, 0.5)
+    slots = rng.integers(0, n_nodes, n_upd)
+    slots[n_upd // 2:n_upd // 2 + 20] = slots[:20]          # repeats: later entries must win
+    op = np.where(rng.random(n_upd) < 0.2, PE_NODE_REMOVE, PE_NODE_SET).astype(np.uint8)
+    cap = np.ascontiguousarray(donor.cap.T)
+    used = np.ascontiguousarray(donor.used.T)
+    labels = donor.labels.copy()
+    island = rng.integers(-1, 50, n_upd).astype(np.int32)
+    return slots, op, cap, used, labels, island
+
+
+def apply_host(res, labels, island, deltas):
+    slots, op, cap, used, lab, isl = deltas
+    res, labels, island = res.copy(), labels.copy(), island.copy()
+    for i in range(len(slots)):
+        s = slots[i]
+        if op[i] == PE_NODE_SET:
+            res[:, s] = cap[i] - used[i]
+            labels[s] = lab[i]
+            island[s] = isl[i]
+        else:
+            res[:, s] = NEVER
+            labels[s] = 0
+            island[s] = -1
+    return res, labels, island
+
+
+def removed_slots(deltas):
+    """The slots whose last entry in the batch is a REMOVE, ascending."""
+    last = {int(s): int(o) for s, o in zip(deltas[0], deltas[1])}
+    return np.array(sorted(s for s, o in last.items() if o == PE_NODE_REMOVE), dtype=np.int64)
+
+
+def mask_bits(mask, nodes):
+    """[J][len(nodes)] the bits of a row-major fit mask ([J][W] uint64) at the given nodes."""
+    nodes = np.asarray(nodes, dtype=np.int64)
+    return (mask[:, nodes // 64] >> (nodes % 64).astype(np.uint64)) & np.uint64(1)
+
+
+class Model:
+    """res [4][N] current residuals, labels [N] with bit 31 from the island, the reset snapshot."""
+
+    def __init__(self, res, labels, island):
+        self.res = np.array(res, dtype=np.int64, copy=True)
+        self.island = np.array(island, dtype=np.int32, copy=True)
+        self.labels = synth.island_labels(labels, self.island)
+        self.res0 = self.res.copy()
+
+    @classmethod
+    def of(cls, inv):
+        return cls(inv.residual(), inv.labels, inv.island)
+
+    @property
+    def n(self):
+        return int(self.res.shape[1])
+
+    def place(self, batch):
+        """pe_place_greedy through the oracle: (pods, status, residuals after); the model keeps them."""
+        pods, st, after = oracle.place_greedy(self.res, self.labels, batch.job_group_off, batch.priority,
+                                              batch.group_count, batch.group_req, batch.group_need)
+        self.res = np.array(after, dtype=np.int64, copy=True)
+        return pods, st, self.res.copy()
+
+    def update(self, deltas):
+        """pe_update_nodes: the current residuals and the snapshot both take the batch."""
+        self.res0, _, _ = apply_host(self.res0, self.labels, self.island, deltas)
+        self.res, labels, self.island = apply_host(self.res, self.labels, self.island, deltas)
+        self.labels = synth.island_labels(labels, self.island)
+
+    def reset(self):
+        self.res = self.res0.copy()
+
+    def fit(self, req, need):
+        """(mask [J][ceil(N / 64)] uint64, counts [J]) of the current residuals, by the oracle."""
+        return oracle.fit_mask(self.res, self.labels, req, need)
+
+    def shard(self, b, e):
+        """The model of the shard context that holds nodes [b, e)."""
+        m = Model(self.res[:, b:e], self.labels[b:e], self.island[b:e])
+        m.res0 = self.res0[:, b:e].copy()
+        return m
+
+
+def row_windows(J):
+    """(row0, n_rows) windows of pe_fit_mask_rows, clipped to J rows: the first and the last row, a
+    window across the first 16-row tile band edge, one whole band, one across the first 64-job band
+    edge, everything but row 0, and the empty window at the end."""
+    out = []
+    for r0, n in [(0, 1), (J - 1, 1), (15, 2), (16, 16), (63, 2), (1, J - 1), (J, 0)]:
+        r0 = min(max(r0, 0), J)
+        n = min(max(n, 0), J - r0)
+        if (r0, n) not in out:
+            out.append((r0, n))
+    return out

@@ -7,41 +7,12 @@ import numpy as np
 import pytest
 
 import oracle
+from inventory_model import apply_host, make_deltas
 from placement import PE_NODE_REMOVE, PE_NODE_SET, Engine, PlacementError, synth
 
 pytestmark = pytest.mark.gpu
 
 NEVER = np.iinfo(np.int64).min
-
-
-def make_deltas(n_nodes, n_upd, seed):
-    """Random SET/REMOVE batch with repeated slots (SET -> REMOVE -> SET chains)."""
-    rng = np.random.default_rng(seed)
-    donor = synth.make_inventory(n_upd, seed + 1, 0.5)
-    slots = rng.integers(0, n_nodes, n_upd)
-    slots[n_upd // 2:n_upd // 2 + 20] = slots[:20]          # repeats: later entries must win
-    op = np.where(rng.random(n_upd) < 0.2, PE_NODE_REMOVE, PE_NODE_SET).astype(np.uint8)
-    cap = np.ascontiguousarray(donor.cap.T)
-    used = np.ascontiguousarray(donor.used.T)
-    labels = donor.labels.copy()
-    island = rng.integers(-1, 50, n_upd).astype(np.int32)
-    return slots, op, cap, used, labels, island
-
-
-def apply_host(res, labels, island, deltas):
-    slots, op, cap, used, lab, isl = deltas
-    res, labels, island = res.copy(), labels.copy(), island.copy()
-    for i in range(len(slots)):
-        s = slots[i]
-        if op[i] == PE_NODE_SET:
-            res[:, s] = cap[i] - used[i]
-            labels[s] = lab[i]
-            island[s] = isl[i]
-        else:
-            res[:, s] = NEVER
-            labels[s] = 0
-            island[s] = -1
-    return res, labels, island
 
 
 def test_update_nodes_fit_greedy_and_snapshot():

@@ -853,6 +853,9 @@ int pe_load_nodes(pe_ctx* ctx, int64_t n, const int64_t* cap, const int64_t* use
     ctx->end = n * (ctx->rank + 1) / ctx->world;
     ctx->Ns = ctx->end - ctx->begin;
     ctx->stride = round_up(std::max<int64_t>(ctx->Ns, 1), 256);
+    // the staged fit batch was planned for the old shard (Wn, Wt, block counts, buffer sizes): a run
+    // or a read with the new Ns is PE_ESTATE until the next pe_jobs_upload / pe_fit_mask
+    ctx->fit_uploaded = false;
     const size_t cells = (size_t)pe::D * (size_t)ctx->stride;
     std::vector<int64_t> r(cells, pe::NEVER);
     std::vector<uint32_t> lab((size_t)ctx->stride, 0u);
