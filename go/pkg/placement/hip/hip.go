@@ -60,6 +60,8 @@ const (
 	NeedIsland  = uint32(C.PE_NEED_ISLAND)
 	// CapMax is where GangCapacity's per-node capacity saturates.
 	CapMax = int32(C.PE_CAP_MAX)
+	// MaxDomains bounds GangCapacityDomains' nDomains.
+	MaxDomains = int32(C.PE_MAX_DOMAINS)
 )
 
 // Node inventory update ops.
@@ -607,6 +609,44 @@ func (e *Engine) GangCapacity(req []int64, need []uint32) (slots []int64, maxNod
 	nodes = make([]int64, J)
 	rc := C.pe_gang_capacity(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr64(slots), ptr32(maxNode), ptr64(nodes))
 	return slots, maxNode, nodes, e.err(rc, "pe_gang_capacity")
+}
+
+// DomainCapacity is GangCapacityDomains' answer; a part that was not asked for is nil.
+type DomainCapacity struct {
+	DomSlots    []int64 // [J][nDomains]: pods of job j's shape that domain k holds
+	DomNodes    []int64 // [J][nDomains]: its nodes holding at least one
+	Domain      []int32 // [J]: the domain with the smallest DomSlots >= count, ties to the smallest id; -1 = none
+	DomainSlots []int64 // [J]: that domain's slots, 0 when none
+	Feasible    []int32 // [J]: domains with DomSlots >= count
+}
+
+// GangCapacityDomains answers GangCapacity's question per topology domain: the domain of a node is its
+// island id in [0, nDomains) as last given by LoadNodes / UpdateNodes; a node with another id, or a
+// removed slot, counts nowhere.  tables asks for the [J][nDomains] tables.  With count ([J], each >= 1)
+// the device also picks, per job, the best-fitting domain; with tables false only those J-sized
+// answers cross.  count nil: no selection.  A sharded engine answers tables only (a domain may span
+// shards: add the shards' tables, then select).  Read-only, like GangCapacity.
+func (e *Engine) GangCapacityDomains(req []int64, need []uint32, count []int32, nDomains int32, tables bool) (*DomainCapacity, error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, fmt.Errorf("GangCapacityDomains: %d needs for %d jobs", len(need), J)
+	}
+	if count != nil && len(count) != J {
+		return nil, fmt.Errorf("GangCapacityDomains: %d counts for %d jobs", len(count), J)
+	}
+	out := &DomainCapacity{}
+	if tables && nDomains >= 1 && nDomains <= MaxDomains {
+		out.DomSlots = make([]int64, J*int(nDomains))
+		out.DomNodes = make([]int64, J*int(nDomains))
+	}
+	if count != nil {
+		out.Domain = make([]int32, J)
+		out.DomainSlots = make([]int64, J)
+		out.Feasible = make([]int32, J)
+	}
+	rc := C.pe_gang_capacity_domains(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(count), C.int32_t(nDomains),
+		ptr64(out.DomSlots), ptr64(out.DomNodes), ptr32(out.Domain), ptr64(out.DomainSlots), ptr32(out.Feasible))
+	return out, e.err(rc, "pe_gang_capacity_domains")
 }
 
 // Gangs is a greedy placement batch: jobs of groups of identical pods (include/placement.h).

@@ -336,6 +336,42 @@ int pe_fit_mask_row_pitch(const pe_ctx* ctx, int64_t* words);
 int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, const uint32_t* need /* or NULL = 0 */,
                      int64_t* out_slots, int32_t* out_max_node, int64_t* out_nodes);
 
+/* (ABI 7, additive) Gang capacity per topology domain: which rack, scale-up domain or xGMI island group
+ * holds a whole gang -- the level between pe_gang_capacity's out_max_node (one node) and out_slots (the
+ * whole shard) that a topology-aware gang scheduler asks about before it admits a training job.
+ * The DOMAIN of node n is island[n] as last given by pe_load_nodes or pe_update_nodes: an id in
+ * [0, n_domains).  A node with island < 0 or island >= n_domains, and a removed slot, belongs to no domain
+ * and counts nowhere.  The island-group greedy of pe_place_greedy (PE_NEED_ISLAND: the gang on ONE node
+ * that has an island) is unchanged; there an island is still a single node.
+ * With cap(j, n) exactly as pe_gang_capacity defines it, against the CURRENT residuals of this shard:
+ *   out_dom_slots[j][k] = sum of cap(j, n) over the nodes n of domain k
+ *   out_dom_nodes[j][k] = number of those nodes with cap(j, n) >= 1
+ * When every island id is below n_domains, the sum over k of out_dom_slots[j][k] is pe_gang_capacity's
+ * out_slots for need[j] | PE_NEED_ISLAND, and the sum of out_dom_nodes[j][k] its out_nodes.
+ * Selection, on the device (only the three J-sized arrays cross for it; a caller who wants just the
+ * answer passes the tables NULL and never pays for J x n_domains values):
+ *   out_domain[j]       = the domain with the smallest out_dom_slots[j][k] >= count[j], ties to the
+ *                         smallest k; -1 if there is none.  Best fit at the domain level: large domains
+ *                         stay free for large gangs.
+ *   out_domain_slots[j] = that domain's slots, 0 when none
+ *   out_feasible[j]     = number of domains with out_dom_slots[j][k] >= count[j]
+ * A non-NULL selection output requires count with every count[j] >= 1, else PE_EINVAL (the first
+ * offending index in pe_last_error); without one, count is not read and may be NULL.
+ * Sharded contexts: the tables are per shard, like pe_gang_capacity's counts -- a domain may span shards
+ * and the caller adds the tables.  Selecting from one shard's table would be wrong, so with
+ * world_size > 1 a non-NULL selection output is PE_EINVAL.
+ * Read-only: residuals and the staged fit-mask state (pe_jobs_upload ... pe_fit_mask_rows) are left as
+ * they are, and the call keeps nothing that a later pe_update_nodes or pe_load_nodes could invalidate.
+ * Each out_* may be NULL; need NULL = 0.  PE_EINVAL: a negative request (the first offending index in
+ * pe_last_error), n_domains outside [1, PE_MAX_DOMAINS].  PE_ESTATE: a call before pe_load_nodes.  An
+ * empty shard or n_jobs == 0 is PE_OK: tables 0, out_domain -1, out_domain_slots and out_feasible 0. */
+#define PE_MAX_DOMAINS 65536
+int pe_gang_capacity_domains(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/,
+                             const uint32_t* need /* or NULL = 0 */, const int32_t* count /*[j] or NULL*/,
+                             int32_t n_domains, int64_t* out_dom_slots /*[j][n_domains] or NULL*/,
+                             int64_t* out_dom_nodes /*[j][n_domains] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
+                             int64_t* out_domain_slots /*[j] or NULL*/, int32_t* out_feasible /*[j] or NULL*/);
+
 /* Greedy best-fit all-or-nothing gang placement.  Jobs in (priority
  * desc, index asc) order, groups of a job in the given order, pods of a group identical.
  *   job_group_off[J+1], priority[J], group_count[G] (pods to place), group_req[G][4],

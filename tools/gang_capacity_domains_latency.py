@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""pe_gang_capacity_domains per-call latency on the cfg5 inventory (1M nodes), in one process: median of N
+calls through the C ABI after a warm-up, tables off (count given: the device selects, J-sized answers
+cross).  Two domain layouts of D = 4096 domains -- contiguous racks (n // ceil(N / D)) and interleaved
+(n % D) -- each at J = 1 and for the cfg5 batch (100 000 jobs), with pe_gang_capacity on the same batch
+in the same process as the yardstick, and the kernels alone (PE_CAP_EVENTS=1: hipEvents on the context
+stream, read back from pe_last_error).  Every step runs under a watchdog of its own that ends the process
+if it overruns.
+    python tools/gang_capacity_domains_latency.py      (GC_NODES / GC_JOBS / GC_DOMAINS / GC_STEP_LIMIT_S to resize)"""
+import ctypes
+import faulthandler
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "training-operator_amd")]
+import bench  # noqa: E402
+from placement import Engine, synth  # noqa: E402
+
+P = ctypes.c_void_p
+LIMIT = int(os.environ.get("GC_STEP_LIMIT_S", "120"))
+NODES = int(os.environ.get("GC_NODES", "1000000"))
+JOBS = int(os.environ.get("GC_JOBS", "100000"))
+DOMAINS = int(os.environ.get("GC_DOMAINS", "4096"))
+
+
+class step:
+    """One GPU step under its own time limit: past it the watchdog thread dumps the stacks and exits."""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __enter__(self):
+        print(f"[{self.name}]", flush=True)
+        faulthandler.dump_traceback_later(LIMIT, exit=True)
+
+    def __exit__(self, *exc):
+        faulthandler.cancel_dump_traceback_later()
+        return False
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(P)
+
+
+def capacity_call(eng, req, need):
+    J = req.shape[0]
+    slots, mx, nodes = np.zeros(J, np.int64), np.zeros(J, np.int32), np.zeros(J, np.int64)
+    args = (eng.h, J, ptr(req), ptr(need), ptr(slots), ptr(mx), ptr(nodes))
+
+    def call():
+        rc = eng.lib.pe_gang_capacity(*args)
+        assert rc == 0, eng.lib.pe_last_error(eng.h)
+    call.keep = (req, need, slots, mx, nodes)
+    return call
+
+
+def domains_call(eng, req, need, count):
+    J = req.shape[0]
+    dom, slots, feas = np.zeros(J, np.int32), np.zeros(J, np.int64), np.zeros(J, np.int32)
+    args = (eng.h, J, ptr(req), ptr(need), ptr(count), DOMAINS, None, None, ptr(dom), ptr(slots), ptr(feas))
+
+    def call():
+        rc = eng.lib.pe_gang_capacity_domains(*args)
+        assert rc == 0, eng.lib.pe_last_error(eng.h)
+    call.keep = (req, need, count, dom, slots, feas)
+    return call
+
+
+def kernel_ms(eng, call, reps, warm):
+    """Median of the kernels' hipEvent time over `reps` calls (PE_CAP_EVENTS=1)."""
+    os.environ["PE_CAP_EVENTS"] = "1"
+    try:
+        ms = []
+        for i in range(warm + reps):
+            call()
+            m = re.search(r"kernels_ms=([0-9.]+)", eng.lib.pe_last_error(eng.h).decode())
+            if i >= warm:
+                ms.append(float(m.group(1)))
+        return sorted(ms)[len(ms) // 2]
+    finally:
+        del os.environ["PE_CAP_EVENTS"]
+
+
+seed = synth.SEED["cfg5"]
+inv = synth.make_inventory(NODES, seed, 0.2)
+req, need = synth.make_fit_jobs(JOBS, seed)
+req, need = np.ascontiguousarray(req, np.int64), np.ascontiguousarray(need, np.uint32)
+count = np.ascontiguousarray(1 + (np.arange(JOBS) % 64) * 8, np.int32)          # gangs of 1 .. 505 pods
+ids = np.arange(NODES, dtype=np.int64)
+per_rack = -(-NODES // DOMAINS)
+layouts = (("contiguous racks", (ids // per_rack).astype(np.int32)), ("interleaved", (ids % DOMAINS).astype(np.int32)))
+
+eng = Engine(0)
+for name, island in layouts:
+    with step(f"load {NODES} nodes, {DOMAINS} domains, {name}"):
+        eng.load_nodes(inv.cap, inv.used, inv.labels, island)
+    for J, reps, warm, kreps in ((1, 500, 30, 100), (JOBS, 20, 3, 10)):
+        with step(f"{name}: J = {J}"):
+            dom = domains_call(eng, req[:J], need[:J], count[:J])
+            first, _ = bench.time_calls(dom, 1, 1)
+            if first > 250e3:   # a slow layout: fewer repetitions, the step stays within its limit
+                reps, warm, kreps = 5, 1, 3
+            med, p90 = bench.time_calls(dom, reps, warm)
+            k = kernel_ms(eng, dom, kreps, 2)
+            yard = capacity_call(eng, req[:J], need[:J])
+            ymed, yp90 = bench.time_calls(yard, reps, warm)
+            yk = kernel_ms(eng, yard, kreps, 2)
+            print(f"{name} J {J}: pe_gang_capacity_domains call {med:.1f} us (p90 {p90:.1f}), kernels {k * 1e3:.1f} us; "
+                  f"pe_gang_capacity call {ymed:.1f} us (p90 {yp90:.1f}), kernels {yk * 1e3:.1f} us; "
+                  f"ratio call {med / ymed:.2f}, kernels {k / yk:.2f}", flush=True)
+eng.close()

@@ -426,6 +426,18 @@ struct pe_ctx {
   std::vector<pe::CapShape> cp_uniq;
   std::vector<int32_t> cp_tab, cp_of;
   hipEvent_t cp_ev[2] = {nullptr, nullptr};   // PE_CAP_EVENTS=1: around the call's kernels
+  // gang capacity per domain (pe_gang_capacity_domains; shapes, dedupe and events are cp_*): the device
+  // tables of one chunk of shapes and their pinned copies, the call's distinct (shape, count) picks with
+  // their answers, the pick dedupe table and each job's pick.  Grow and are reused; nothing outlives a call.
+  DevBuf<uint64_t> dm_table;   // per launch of sc shapes: slots u64 [sc][D], then nodes u32 [sc][D]
+  HostBuf<uint64_t> dm_hslots;
+  HostBuf<uint32_t> dm_hnodes;
+  HostBuf<pe::DomPick> dm_hpicks;
+  DevBuf<pe::DomPick> dm_picks;
+  DevBuf<pe::DomSel> dm_sel;
+  HostBuf<pe::DomSel> dm_hsel;
+  std::vector<pe::DomPick> dm_upicks;
+  std::vector<int32_t> dm_ptab, dm_pof;
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -497,6 +509,8 @@ struct pe_ctx {
     a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
     aw_stage.release(); aw_outh.release(); aw_dev.release();
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
+    dm_table.release(); dm_hslots.release(); dm_hnodes.release(); dm_hpicks.release();
+    dm_picks.release(); dm_sel.release(); dm_hsel.release();
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -2670,6 +2684,55 @@ int pe_fit_mask(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t*
   });
 }
 
+// The batch's distinct (request, need) shapes in first-seen order -> ctx->cp_uniq (with the reciprocals of
+// their requests), each job's shape -> ctx->cp_of; returns their number.  Shared by pe_gang_capacity and
+// pe_gang_capacity_domains.
+static int64_t cap_dedupe(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need) {
+  // distinct shapes, in first-seen order (open addressing; a job equal to its predecessor skips the probe)
+  auto& uniq = ctx->cp_uniq;
+  auto& of = ctx->cp_of;
+  auto& tab = ctx->cp_tab;
+  uniq.clear();
+  of.resize((size_t)n_jobs);
+  size_t cap = 16;
+  while (cap < (size_t)n_jobs * 2) cap <<= 1;
+  tab.assign(cap, -1);
+  auto same = [&](const pe::CapShape& s, const int64_t* q, uint32_t nd) {
+    return s.q[0] == q[0] && s.q[1] == q[1] && s.q[2] == q[2] && s.q[3] == q[3] && s.need == nd;
+  };
+  for (int64_t j = 0; j < n_jobs; ++j) {
+    const int64_t* q = req + j * pe::D;
+    const uint32_t nd = need ? need[j] : 0u;
+    if (j > 0 && same(uniq[(size_t)of[(size_t)j - 1]], q, nd)) {
+      of[(size_t)j] = of[(size_t)j - 1];
+      continue;
+    }
+    uint64_t h = nd;
+    for (int d = 0; d < pe::D; ++d) {
+      h = (h ^ (uint64_t)q[d]) * 0x9E3779B97F4A7C15ull;
+      h ^= h >> 29;
+    }
+    size_t at = (size_t)h & (cap - 1);
+    while (tab[at] >= 0 && !same(uniq[(size_t)tab[at]], q, nd)) at = (at + 1) & (cap - 1);
+    if (tab[at] < 0) {
+      tab[at] = (int32_t)uniq.size();
+      pe::CapShape sp{};
+      for (int d = 0; d < pe::D; ++d) {
+        sp.q[d] = q[d];
+        if (q[d] > 0) {
+          const pe::DivMagic dm = pe::div_magic((uint64_t)q[d]);
+          sp.m[d] = dm.m;
+          sp.sh[d] = dm.shift;
+        }
+      }
+      sp.need = nd;
+      uniq.push_back(sp);
+    }
+    of[(size_t)j] = tab[at];
+  }
+  return (int64_t)uniq.size();
+}
+
 // Gang capacity: the distinct (request, need) shapes of the batch go to the device with the
 // reciprocals of their requests (pe_divmagic.h), gang_capacity_kernel answers per shape over the
 // shard's current residuals, and the host scatters the answers back to the jobs.  Own buffers: the
@@ -2685,49 +2748,9 @@ int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint
     if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
     need_ptr(req, "req");
     check_req(req, n_jobs, "req");
-    // distinct shapes, in first-seen order (open addressing; a job equal to its predecessor skips the probe)
-    auto& uniq = ctx->cp_uniq;
-    auto& of = ctx->cp_of;
-    auto& tab = ctx->cp_tab;
-    uniq.clear();
-    of.resize((size_t)n_jobs);
-    size_t cap = 16;
-    while (cap < (size_t)n_jobs * 2) cap <<= 1;
-    tab.assign(cap, -1);
-    auto same = [&](const pe::CapShape& s, const int64_t* q, uint32_t nd) {
-      return s.q[0] == q[0] && s.q[1] == q[1] && s.q[2] == q[2] && s.q[3] == q[3] && s.need == nd;
-    };
-    for (int64_t j = 0; j < n_jobs; ++j) {
-      const int64_t* q = req + j * pe::D;
-      const uint32_t nd = need ? need[j] : 0u;
-      if (j > 0 && same(uniq[(size_t)of[(size_t)j - 1]], q, nd)) {
-        of[(size_t)j] = of[(size_t)j - 1];
-        continue;
-      }
-      uint64_t h = nd;
-      for (int d = 0; d < pe::D; ++d) {
-        h = (h ^ (uint64_t)q[d]) * 0x9E3779B97F4A7C15ull;
-        h ^= h >> 29;
-      }
-      size_t at = (size_t)h & (cap - 1);
-      while (tab[at] >= 0 && !same(uniq[(size_t)tab[at]], q, nd)) at = (at + 1) & (cap - 1);
-      if (tab[at] < 0) {
-        tab[at] = (int32_t)uniq.size();
-        pe::CapShape sp{};
-        for (int d = 0; d < pe::D; ++d) {
-          sp.q[d] = q[d];
-          if (q[d] > 0) {
-            const pe::DivMagic dm = pe::div_magic((uint64_t)q[d]);
-            sp.m[d] = dm.m;
-            sp.sh[d] = dm.shift;
-          }
-        }
-        sp.need = nd;
-        uniq.push_back(sp);
-      }
-      of[(size_t)j] = tab[at];
-    }
-    const int64_t S = (int64_t)uniq.size();
+    const int64_t S = cap_dedupe(ctx, n_jobs, req, need);
+    const auto& uniq = ctx->cp_uniq;
+    const auto& of = ctx->cp_of;
     const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
     float kernel_ms = 0.f;
     hipchk(ctx->cp_hout.ensure((size_t)S), "alloc pinned capacity results");
@@ -2770,6 +2793,165 @@ int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint
       if (out_nodes) out_nodes[j] = (int64_t)r.nodes;
     }
     if (events) ctx->err = "S=" + std::to_string(S) + " kernels_ms=" + std::to_string(kernel_ms);
+    return PE_OK;
+  });
+}
+
+// Gang capacity per topology domain: pe_gang_capacity's distinct shapes (cap_dedupe) go to the device,
+// gang_capacity_domains_kernel adds every node's capacity to the [shape][domain] tables of its island id
+// (pe_domains.hip) and, for a selection, domain_select_kernel answers each distinct (shape, count) from the
+// shape's row, so only J-sized results cross.  The tables exist on the device for one chunk of shapes at a
+// time (64 MiB at most); a requested table is copied out per chunk and scattered to the jobs here.
+// Nothing is kept between calls, and neither the residuals nor the staged fit-mask state are touched.
+// PE_CAP_EVENTS=1: as pe_gang_capacity.
+int pe_gang_capacity_domains(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, const int32_t* count,
+                             int32_t n_domains, int64_t* out_dom_slots, int64_t* out_dom_nodes, int32_t* out_domain,
+                             int64_t* out_domain_slots, int32_t* out_feasible) {
+  return guarded(ctx, [&]() -> int {
+    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    if (n_domains < 1 || n_domains > PE_MAX_DOMAINS) raise(PE_EINVAL, "n_domains outside [1, PE_MAX_DOMAINS]");
+    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
+    const bool select = out_domain || out_domain_slots || out_feasible;
+    const bool tables = out_dom_slots || out_dom_nodes;
+    if (select && ctx->world > 1)
+      raise(PE_EINVAL, "selection outputs on a sharded context: a domain may span shards (add the tables, then select)");
+    if (n_jobs == 0) return PE_OK;
+    if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
+    need_ptr(req, "req");
+    check_req(req, n_jobs, "req");
+    if (select) {
+      need_ptr(count, "count");
+      const int64_t i = first_bad(n_jobs, [count](int64_t k) { return count[k] < 1; });
+      if (i < n_jobs) raise(PE_EINVAL, "count: value below 1 at index " + std::to_string(i));
+    }
+    const int64_t Dn = n_domains;
+    if (ctx->Ns == 0) {   // an empty shard holds nothing
+      if (out_dom_slots) std::memset(out_dom_slots, 0, (size_t)(n_jobs * Dn) * sizeof(int64_t));
+      if (out_dom_nodes) std::memset(out_dom_nodes, 0, (size_t)(n_jobs * Dn) * sizeof(int64_t));
+      for (int64_t j = 0; j < n_jobs; ++j) {
+        if (out_domain) out_domain[j] = -1;
+        if (out_domain_slots) out_domain_slots[j] = 0;
+        if (out_feasible) out_feasible[j] = 0;
+      }
+      return PE_OK;
+    }
+    const int64_t S = cap_dedupe(ctx, n_jobs, req, need);
+    const auto& of = ctx->cp_of;
+    // distinct (shape, count) picks, in first-seen order
+    auto& picks = ctx->dm_upicks;
+    auto& pof = ctx->dm_pof;
+    picks.clear();
+    if (select) {
+      auto& tab = ctx->dm_ptab;
+      pof.resize((size_t)n_jobs);
+      size_t cap = 16;
+      while (cap < (size_t)n_jobs * 2) cap <<= 1;
+      tab.assign(cap, -1);
+      for (int64_t j = 0; j < n_jobs; ++j) {
+        const uint32_t sh = (uint32_t)of[(size_t)j];
+        const int32_t c = count[j];
+        if (j > 0 && picks[(size_t)pof[(size_t)j - 1]].shape == sh && picks[(size_t)pof[(size_t)j - 1]].count == c) {
+          pof[(size_t)j] = pof[(size_t)j - 1];
+          continue;
+        }
+        uint64_t h = (((uint64_t)sh << 32) | (uint32_t)c) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+        size_t at = (size_t)h & (cap - 1);
+        while (tab[at] >= 0 && !(picks[(size_t)tab[at]].shape == sh && picks[(size_t)tab[at]].count == c))
+          at = (at + 1) & (cap - 1);
+        if (tab[at] < 0) {
+          tab[at] = (int32_t)picks.size();
+          picks.push_back(pe::DomPick{sh, c});
+        }
+        pof[(size_t)j] = tab[at];
+      }
+    }
+    const int64_t P = (int64_t)picks.size();
+    const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
+    float kernel_ms = 0.f;
+    hipchk(ctx->cp_hshapes.ensure((size_t)S), "alloc pinned shapes");
+    hipchk(ctx->cp_shapes.ensure((size_t)S), "alloc shapes");
+    std::memcpy((void*)ctx->cp_hshapes.p, ctx->cp_uniq.data(), (size_t)S * sizeof(pe::CapShape));
+    // shapes per launch: the two tables (12 B per shape and domain) stay within 64 MiB (16 shapes at least)
+    const int64_t fit64 = (int64_t(64) << 20) / (12 * Dn);
+    const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(16, fit64));
+    hipchk(ctx->dm_table.ensure((size_t)(chunk * Dn + (chunk * Dn + 1) / 2)), "alloc domain tables");
+    if (out_dom_slots) hipchk(ctx->dm_hslots.ensure((size_t)(chunk * Dn)), "alloc pinned domain slots");
+    if (out_dom_nodes) hipchk(ctx->dm_hnodes.ensure((size_t)(chunk * Dn)), "alloc pinned domain nodes");
+    hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)S * sizeof(pe::CapShape), hipMemcpyHostToDevice,
+                          ctx->stream),
+           "H2D shapes");
+    if (select) {
+      hipchk(ctx->dm_hpicks.ensure((size_t)P), "alloc pinned picks");
+      hipchk(ctx->dm_picks.ensure((size_t)P), "alloc picks");
+      hipchk(ctx->dm_sel.ensure((size_t)P), "alloc selections");
+      hipchk(ctx->dm_hsel.ensure((size_t)P), "alloc pinned selections");
+      std::memcpy((void*)ctx->dm_hpicks.p, picks.data(), (size_t)P * sizeof(pe::DomPick));
+      hipchk(hipMemcpyAsync(ctx->dm_picks.p, ctx->dm_hpicks.p, (size_t)P * sizeof(pe::DomPick), hipMemcpyHostToDevice,
+                            ctx->stream),
+             "H2D picks");
+    }
+    if (events) {
+      for (hipEvent_t& e : ctx->cp_ev)
+        if (!e) hipchk(hipEventCreate(&e), "event create");
+      hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
+    }
+    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+      const int64_t sc = std::min(chunk, S - s0);
+      // the launch's two tables, adjacent: one memset.  The node table exists only for a caller who reads it
+      // (the selection reads the slots alone): without it the flush costs half the global atomics.
+      uint64_t* const d_slots = ctx->dm_table.p;
+      uint32_t* const d_nodes = out_dom_nodes ? (uint32_t*)(d_slots + sc * Dn) : nullptr;
+      hipchk(hipMemsetAsync(d_slots, 0, (size_t)(sc * Dn) * (sizeof(uint64_t) + (d_nodes ? sizeof(uint32_t) : 0)),
+                            ctx->stream),
+             "zero domain tables");
+      hipchk(pe::launch_gang_capacity_domains(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
+                                              ctx->cp_shapes.p + s0, sc, n_domains, d_slots, d_nodes),
+             "launch gang_capacity_domains");
+      if (select)
+        hipchk(pe::launch_domain_select(ctx->stream, d_slots, s0, sc, n_domains, ctx->dm_picks.p, P,
+                                        ctx->dm_sel.p),
+               "launch domain_select");
+      if (!tables) continue;
+      if (out_dom_slots)
+        hipchk(hipMemcpyAsync(ctx->dm_hslots.p, d_slots, (size_t)(sc * Dn) * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, ctx->stream),
+               "D2H domain slots");
+      if (out_dom_nodes)
+        hipchk(hipMemcpyAsync(ctx->dm_hnodes.p, d_nodes, (size_t)(sc * Dn) * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, ctx->stream),
+               "D2H domain nodes");
+      hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_domains");
+      for (int64_t j = 0; j < n_jobs; ++j) {   // the chunk's rows to their jobs
+        const int64_t s = (int64_t)of[(size_t)j] - s0;
+        if (s < 0 || s >= sc) continue;
+        if (out_dom_slots)   // below 2^55: the bits are the int64's
+          std::memcpy(out_dom_slots + j * Dn, (const void*)(ctx->dm_hslots.p + s * Dn), (size_t)Dn * sizeof(int64_t));
+        if (out_dom_nodes) {
+          const uint32_t* row = ctx->dm_hnodes.p + s * Dn;
+          int64_t* o = out_dom_nodes + j * Dn;
+          for (int64_t k = 0; k < Dn; ++k) o[k] = (int64_t)row[k];
+        }
+      }
+    }
+    if (events) hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
+    if (select)
+      hipchk(hipMemcpyAsync(ctx->dm_hsel.p, ctx->dm_sel.p, (size_t)P * sizeof(pe::DomSel), hipMemcpyDeviceToHost,
+                            ctx->stream),
+             "D2H selections");
+    hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_domains");
+    if (events) hipchk(hipEventElapsedTime(&kernel_ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
+    if (select) {
+      const pe::DomSel* a = ctx->dm_hsel.p;
+      for (int64_t j = 0; j < n_jobs; ++j) {
+        const pe::DomSel& r = a[pof[(size_t)j]];
+        if (out_domain) out_domain[j] = r.domain;
+        if (out_domain_slots) out_domain_slots[j] = (int64_t)r.slots;
+        if (out_feasible) out_feasible[j] = (int32_t)r.feasible;
+      }
+    }
+    if (events)
+      ctx->err = "S=" + std::to_string(S) + " P=" + std::to_string(P) + " kernels_ms=" + std::to_string(kernel_ms);
     return PE_OK;
   });
 }

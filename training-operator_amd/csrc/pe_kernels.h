@@ -466,4 +466,26 @@ static_assert(sizeof(CapAcc) == 16, "CapAcc must be 16 B");
 hipError_t launch_gang_capacity(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
                                 const CapShape* shapes, int64_t S, CapAcc* partials, CapAcc* out);
 
+// ---- gang capacity per topology domain (pe_gang_capacity_domains, pe_domains.hip)
+constexpr int DM_MAX_DOMAINS = 65536;            // PE_MAX_DOMAINS
+// A distinct (shape, count) of a call that asks for a selection; its answer.
+struct DomPick {
+  uint32_t shape;   // index into the call's distinct shapes
+  int32_t count;    // >= 1
+};
+struct DomSel {
+  uint64_t slots;     // the chosen domain's slots, 0 when none
+  int32_t domain;     // smallest dom_slots >= count, ties to the smallest id; -1 when none
+  uint32_t feasible;  // domains with dom_slots >= count
+};
+static_assert(sizeof(DomPick) == 8 && sizeof(DomSel) == 16, "DomPick / DomSel layout");
+// dom_slots / dom_nodes [S][n_domains] += over the shard's Ns nodes (the caller zeroes them; dom_nodes may be
+// NULL: not computed), domain of node n = island[n].
+hipError_t launch_gang_capacity_domains(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
+                                        const int32_t* island, int64_t Ns, const CapShape* shapes, int64_t S,
+                                        int n_domains, uint64_t* dom_slots, uint32_t* dom_nodes);
+// out[p] for every pick p < P whose shape lies in [s0, s0 + S), from the rows dom_slots[shape - s0].
+hipError_t launch_domain_select(hipStream_t s, const uint64_t* dom_slots, int64_t s0, int64_t S, int n_domains,
+                                const DomPick* picks, int64_t P, DomSel* out);
+
 }  // namespace pe

@@ -11,19 +11,20 @@ Every call runs on the GPU through include/placement.h; nothing here computes a 
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
 
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
-           "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs"]
+           "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
+           "select_domain"]
 
 
 class PlacementError(RuntimeError):
@@ -67,6 +68,35 @@ def wide_limbs(values):
         fl[i] = x & (2**64 - 1)
         fh[i] = x >> 64
     return lo, hi
+
+
+class DomainCapacity(NamedTuple):
+    """Engine.gang_capacity_domains' answer; a part that was not asked for is None."""
+    dom_slots: Optional[np.ndarray]      # int64 [J][n_domains]: pods of job j's shape that domain k holds
+    dom_nodes: Optional[np.ndarray]      # int64 [J][n_domains]: its nodes holding at least one
+    domain: Optional[np.ndarray]         # int32 [J]: smallest dom_slots >= count, ties to the smallest id; -1 = none
+    domain_slots: Optional[np.ndarray]   # int64 [J]: that domain's slots, 0 when none
+    feasible: Optional[np.ndarray]       # int32 [J]: domains with dom_slots >= count
+
+
+def select_domain(dom_slots, count):
+    """The selection rule of pe_gang_capacity_domains on a host table: for the shards' dom_slots tables
+    ADDED UP ([J][n_domains]; a domain may span shards, so one shard's table must not be selected from)
+    and count [J] >= 1, (domain int32[J], domain_slots int64[J], feasible int32[J]) -- the domain with
+    the smallest dom_slots >= count, ties to the smallest id, -1 / 0 when none, and how many domains
+    hold the gang."""
+    t = np.asarray(dom_slots, dtype=np.int64)
+    cnt = np.asarray(count, dtype=np.int64).reshape(-1)
+    if t.ndim != 2 or cnt.shape != (t.shape[0],):
+        raise ValueError("dom_slots must be [J][n_domains] and count [J]")
+    if (cnt < 1).any():
+        raise ValueError("count must be >= 1")
+    ok = t >= cnt[:, None]
+    feasible = ok.sum(axis=1).astype(np.int32)
+    masked = np.where(ok, t, np.iinfo(np.int64).max)
+    domain = np.where(feasible > 0, masked.argmin(axis=1) if t.shape[1] else 0, -1).astype(np.int32)   # argmin: first of equals
+    slots = np.where(feasible > 0, masked.min(axis=1) if t.shape[1] else 0, 0).astype(np.int64)
+    return domain, slots, feasible
 
 
 def comm_id() -> bytes:
@@ -359,6 +389,36 @@ class Engine:
         self._chk(self.lib.pe_gang_capacity(self.h, J, _p(req), _p(nd), _p(slots), _p(max_node), _p(nodes)),
                   "pe_gang_capacity")
         return slots, max_node, nodes
+
+    def gang_capacity_domains(self, req, need=None, count=None, n_domains=None, tables=True) -> DomainCapacity:
+        """pe_gang_capacity_domains: gang capacity per topology domain, the domain of a node being its
+        island id in [0, n_domains).  With tables=True the [J][n_domains] tables dom_slots / dom_nodes come
+        back; with count ([J], >= 1) the device also selects per job the best-fitting domain (domain,
+        domain_slots, feasible) -- with tables=False nothing but those J-sized answers crosses.  On a
+        sharded context only the tables are available: add them over the shards and use select_domain.
+        Read-only, like gang_capacity."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        if n_domains is None:
+            raise ValueError("n_domains is required")
+        cnt = None if count is None else _c(count, np.int32)
+        if cnt is not None and cnt.shape != (J,):
+            raise ValueError("count must be [J]")
+        D = int(n_domains)
+        big = tables and 1 <= D <= PE_MAX_DOMAINS   # (an n_domains the engine refuses allocates nothing here)
+        dom_slots = np.zeros((J, D), dtype=np.int64) if big else None
+        dom_nodes = np.zeros((J, D), dtype=np.int64) if big else None
+        sel = cnt is not None
+        domain = np.full(J, -1, dtype=np.int32) if sel else None
+        domain_slots = np.zeros(J, dtype=np.int64) if sel else None
+        feasible = np.zeros(J, dtype=np.int32) if sel else None
+        self._chk(self.lib.pe_gang_capacity_domains(self.h, J, _p(req), _p(nd), _p(cnt), D, _p(dom_slots), _p(dom_nodes),
+                                                    _p(domain), _p(domain_slots), _p(feasible)),
+                  "pe_gang_capacity_domains")
+        return DomainCapacity(dom_slots, dom_nodes, domain, domain_slots, feasible)
 
     # ------------------------------------------------------------ greedy
     def place_greedy(self, job_group_off, priority, group_count, group_req, group_need=None):
