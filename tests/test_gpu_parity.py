@@ -384,7 +384,7 @@ def test_greedy_vs_oracle(eng, mix, N, J, gpu_frac):
 @pytest.mark.parametrize("mix,topk", [("gang8", 8), ("island8", 16), ("gang8", 600)])
 def test_greedy_list_growth(monkeypatch, mix, topk):
     """Whole-node gangs exhaust short candidate lists (rescans); after the first rescan the engine walks
-    lists of 2 x topk (capped at 1023) for the rest of the batch (pe_engine.cpp, one GPU).  Both ways
+    lists of 2 x topk (capped at 1023) for the rest of the batch (pe_engine_greedy.cpp, one GPU).  Both ways
     bit-exact vs the oracle; growth never rescans more than the fixed length."""
     inv = synth.make_inventory(3000, 71, 1.0)
     batch = synth.make_jobs(400, 73, mix)

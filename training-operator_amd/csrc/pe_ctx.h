@@ -1,0 +1,546 @@
+// libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp): device and
+// pinned buffers, the helper threads, error mapping and the context itself.  Not part of the ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <immintrin.h>
+#include <pthread.h>
+#include <sched.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "pe_hostx.h"
+#include "pe_kernels.h"
+#include "pe_resolver.h"
+#include "placement.h"
+
+// (a namespace of their own: the inline functions below are visible outside the shared library, where
+// plain names such as hipchk could meet another library's)
+namespace pe_engine {
+
+using pe::ReqRec;
+
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  // flags: hipExtMallocWithFlags flags (hipDeviceMallocContiguous falls back to a plain hipMalloc
+  // when the driver cannot provide it)
+  hipError_t ensure(size_t count, unsigned flags = 0) {
+    if (count <= n && p) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    hipError_t e = hipErrorOutOfMemory;
+    if (flags) {
+      e = hipExtMallocWithFlags((void**)&p, bytes, flags);
+      if (e != hipSuccess) (void)hipGetLastError();
+    }
+    if (e != hipSuccess) e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+};
+
+// Pinned host buffer.  Coherent (fine-grained) ones are also read and written by kernels directly
+// (dev = the device-side address): per-window inputs and the candidate blob skip the copy engines.
+template <class T>
+struct HostBuf {
+  T* p = nullptr;
+  T* dev = nullptr;
+  size_t n = 0;
+  hipError_t ensure(size_t count, unsigned flags = hipHostMallocDefault) {
+    if (count <= n && p) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = dev = nullptr;
+    n = 0;
+    hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T), flags);
+    // zeroed: several of these buffers carry completion flags (signalled groups, the aggregation
+    // flag) that a recycled allocation could otherwise hold from an earlier engine's generations
+    if (e == hipSuccess) std::memset((void*)p, 0, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dev, p, 0);
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = dev = nullptr;
+    n = 0;
+  }
+};
+constexpr unsigned kZeroCopy = hipHostMallocCoherent | hipHostMallocMapped;
+
+// One helper thread that runs a posted task while the caller does other work (pipelined greedy:
+// the next window's launches are issued while the host resolves the current one).  Spin handoff:
+// the wake-up of a sleeping thread would cost about as much as the launches it hides.
+class SpinWorker {
+ public:
+  explicit SpinWorker(int device) : th_([this, device] {
+    (void)hipSetDevice(device);   // the current device is per thread
+    loop();
+  }) {}
+  ~SpinWorker() {
+    while (state_.load(std::memory_order_acquire) == 1) _mm_pause();   // a posted task finishes first
+    state_.store(3, std::memory_order_release);
+    th_.join();
+  }
+  void pin(const cpu_set_t& set) { (void)pthread_setaffinity_np(th_.native_handle(), sizeof(set), &set); }
+  void post(std::function<void()> f) {
+    task_ = std::move(f);
+    err_ = nullptr;
+    posted_ = true;
+    state_.store(1, std::memory_order_release);
+  }
+  bool busy() const { return state_.load(std::memory_order_acquire) == 1; }   // a posted task not done yet
+  bool failed() const { return state_.load(std::memory_order_acquire) == 2 && err_ != nullptr; }
+  void wait() {   // rethrows what the task threw; returns at once when nothing is posted
+    if (!posted_) return;
+    posted_ = false;
+    for (int spin = 0; state_.load(std::memory_order_acquire) != 2; ++spin)
+      if (spin < 4096) _mm_pause();
+      else std::this_thread::yield();   // the helper is not running (oversubscribed host)
+    state_.store(0, std::memory_order_relaxed);
+    if (err_) std::rethrow_exception(err_);
+  }
+
+ private:
+  void loop() {
+    int idle = 0;
+    for (;;) {
+      const int st = state_.load(std::memory_order_acquire);
+      if (st == 3) return;
+      if (st != 1) {
+        if (++idle < 4096) _mm_pause();
+        else std::this_thread::yield();   // long idle (host resolving): let others run
+        continue;
+      }
+      idle = 0;
+      try {
+        task_();
+      } catch (...) {
+        err_ = std::current_exception();
+      }
+      state_.store(2, std::memory_order_release);
+    }
+  }
+  std::atomic<int> state_{0};
+  bool posted_ = false;   // (the posting thread's own view: a task posted and not waited for yet)
+  std::function<void()> task_;
+  std::exception_ptr err_;
+  std::thread th_;   // last: starts after the members above exist
+};
+
+// A SpinWorker with a queue: post() does not wait for the previous task (up to kCap in flight), the
+// tasks run in order on the thread, wait() waits for all of them.  After a task threw, the rest are
+// skipped and wait() rethrows.  (The host-merged zero-copy exchange: the main thread posts each
+// window's merge as it launches the window, without waiting for the previous merge to finish.)
+class SpinQueue {
+ public:
+  static constexpr unsigned kCap = 8;
+  explicit SpinQueue(int device) : th_([this, device] {
+    (void)hipSetDevice(device);
+    loop();
+  }) {}
+  ~SpinQueue() {
+    while (busy()) _mm_pause();
+    stop_.store(true, std::memory_order_release);
+    th_.join();
+  }
+  void pin(const cpu_set_t& set) { (void)pthread_setaffinity_np(th_.native_handle(), sizeof(set), &set); }
+  void post(std::function<void()> f) {
+    const unsigned t = tail_.load(std::memory_order_relaxed);
+    while (t - head_.load(std::memory_order_acquire) >= kCap) _mm_pause();   // full: the oldest first
+    q_[t % kCap] = std::move(f);
+    tail_.store(t + 1, std::memory_order_release);
+  }
+  bool busy() const { return head_.load(std::memory_order_acquire) != tail_.load(std::memory_order_acquire); }
+  bool failed() const { return failed_.load(std::memory_order_acquire); }
+  void wait() {   // every posted task done; rethrows the first error (once)
+    for (int spin = 0; busy(); ++spin)
+      if (spin < 4096) _mm_pause();
+      else std::this_thread::yield();
+    if (failed_.load(std::memory_order_acquire)) {
+      failed_.store(false, std::memory_order_relaxed);
+      std::exception_ptr e = err_;
+      err_ = nullptr;
+      if (e) std::rethrow_exception(e);
+    }
+  }
+
+ private:
+  void loop() {
+    int idle = 0;
+    for (;;) {
+      const unsigned h = head_.load(std::memory_order_relaxed);
+      if (h == tail_.load(std::memory_order_acquire)) {
+        if (stop_.load(std::memory_order_acquire)) return;
+        if (++idle < 4096) _mm_pause();
+        else std::this_thread::yield();
+        continue;
+      }
+      idle = 0;
+      if (!failed_.load(std::memory_order_relaxed)) {
+        try {
+          q_[h % kCap]();
+        } catch (...) {
+          err_ = std::current_exception();
+          failed_.store(true, std::memory_order_release);
+        }
+      }
+      q_[h % kCap] = nullptr;
+      head_.store(h + 1, std::memory_order_release);
+    }
+  }
+  std::function<void()> q_[kCap];
+  std::atomic<unsigned> head_{0}, tail_{0};
+  std::atomic<bool> failed_{false}, stop_{false};
+  std::exception_ptr err_;
+  std::thread th_;   // last: starts after the members above exist
+};
+
+
+struct PeError {
+  int code;
+  std::string msg;
+};
+
+[[noreturn]] inline void raise(int code, const std::string& msg) { throw PeError{code, msg}; }
+
+inline void hipchk(hipError_t e, const char* what) {
+  if (e != hipSuccess) raise(PE_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+inline void ncclchk(ncclResult_t r, const char* what) {
+  if (r != ncclSuccess) raise(PE_ERCCL, std::string(what) + ": " + ncclGetErrorString(r));
+}
+
+// Bound of one RCCL window of the greedy: PE_RCCL_TIMEOUT_S seconds (default 60) blocked on a window
+// whose all-gather has not completed (a peer lost mid-batch) -- then the communicator is aborted and
+// the call returns PE_ERCCL.
+inline double rccl_timeout_s() {
+  const char* e = std::getenv("PE_RCCL_TIMEOUT_S");
+  const double s = e ? std::atof(e) : 60.0;
+  return s > 0 ? s : 60.0;
+}
+
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// pe_config.fit_path_mask bits
+constexpr int kMaxMergers = 7;   // zero-copy exchange: merge helper threads per rank (at most)
+constexpr int PATH_I64 = 1, PATH_I32 = 2, PATH_CODED = 4, PATH_NO_THERM = 8, PATH_PLANES = 16, PATH_PLANES_BLOCKS = 32,
+              PATH_LDS = 64;
+constexpr int PATHS_ALL = PATH_I64 | PATH_I32 | PATH_CODED | PATH_PLANES | PATH_LDS;
+
+// One segment of the packed aggregation batch (pe_kernels.h AggSegHdr).
+struct AggSeg {
+  int64_t j0;
+  int32_t nj, ng, nc;
+  int64_t bytes;
+  bool narrow;            // the request section narrowed (pe_kernels.h agg_seg_layout), shifts in sh
+  uint8_t sh[pe::AGG_MAX_KEYS];
+};
+
+}  // namespace pe_engine
+using namespace pe_engine;
+
+struct pe_ctx {
+  std::mutex mu;
+  int device = 0;
+  int rank = 0, world = 1;
+  ncclComm_t comm = nullptr;
+  // a greedy window's collective timed out: the communicator was handed to comm_abort (ncclCommAbort
+  // on its own thread -- it returns once the device work it aborts has drained) and every later
+  // sharded call fails with PE_ERCCL; the caller rebuilds the context (e.g. on the host exchange)
+  bool comm_aborted = false;
+  std::thread comm_abort;
+  std::unique_ptr<pe::Resolver> resolver;   // the greedy's host resolver, reset per batch
+  pe_allgather_fn exchange = nullptr;
+  void* exchange_user = nullptr;
+  void* zc_hx = nullptr;   // the shared-memory exchange whose zero-copy use the ranks agreed on (zc_ok)
+  bool zc_ok = false;
+  int topk = 256, window_groups = 112;
+  bool pipeline = true;   // greedy: scan window w+1 while the host resolves window w (greedy_flags bit0 = off)
+  int64_t window_pods = 1024;
+  int64_t max_nodes = 0;
+  std::string gpu_name, err;
+  hipStream_t stream = nullptr;
+  // inventory shard
+  int64_t n_total = 0, begin = 0, end = 0, Ns = 0, stride = 0;
+  bool loaded = false;
+  // host mirror of the GLOBAL inventory (node states by id, and the reset copy): the greedy
+  // windows ship candidate keys only and the resolver reads node states here
+  std::vector<pe::NodeState, pe::HugeAlloc<pe::NodeState>> m_nodes, m_nodes0;   // (2 MiB pages: random reads)
+  DevBuf<int64_t> res0, res;
+  DevBuf<uint32_t> labels;
+  DevBuf<int32_t> island;
+  DevBuf<pe::NodeUpd> n_upd;   // pe_update_nodes staging
+  // fit mask
+  int64_t fit_J = 0, fit_Jp = 0, Wn = 0, Wt = 0;
+  bool fit_uploaded = false;
+  DevBuf<ReqRec> fit_jobs;
+  DevBuf<pe::ReqRec32> fit_jobs32;
+  DevBuf<int32_t> res32;
+  bool fit32 = false;      // batch is exactly representable in 32 bits (see ReqRec32)
+  int fit_shift[pe::D] = {0, 0, 0, 0};
+  int fit_path = 0;        // 0 int64 compare, 1 int32 compare, 2 dictionary-coded, 3 bit planes, 4 LDS digit planes
+  // LDS digit-plane path (pe_kernels.h LdsSpec): spec, node-block geometry, codes, ranks
+  pe::LdsSpec lds{};
+  int lds_W = 4;                          // u32 words per lane per plane: block = 2048 W nodes
+  int lds_shape[4] = {0, 0, 0, 0};        // fields with 4 / 3 / 2 / 1 digit levels (kernel template)
+  int64_t lds_nblk = 0, lds_R = 1, lds_Tpad = 0, lds_npad = 0, lds_pitch = 0;   // pitch in u64 words
+  DevBuf<pe::LdsSpec> lds_spec_d;
+  DevBuf<int64_t> lds_vals;
+  DevBuf<uint16_t> lds_codes;
+  DevBuf<uint32_t> lds_ranks, lds_aux, lds_slots;   // lds_slots: the fit kernel's per-job u32 count slots
+  DevBuf<uint32_t> lds_rows;                         // the job (mask row) of each count slot, ~0 = none
+  int num_cu = 256;
+  int fit_path_mask = PATHS_ALL;   // allowed paths (pe_config.fit_path_mask)
+  pe::PlaneSpec plane{};
+  int64_t pl_nblk = 0;                   // planes path: 8192-node blocks
+  bool pl_rows = true;                   // planes path: row-major sweep kernel (else block-major streams)
+  int64_t pl_R = 1;                      // row-major kernel: job phases of the uploaded batch
+  int64_t pl_pitch = 0;                  // row-major mask pitch in 8192-node blocks (>= pl_nblk)
+  // A batch with more than PL_MAX distinct (dimension, value) pairs is split into plane sets of at
+  // most PL_MAX pairs each (row-major layout only); each set is encoded and swept on its own by
+  // the indexed-row kernel, its jobs' codes carrying their mask rows.
+  struct PlaneSet {
+    pe::PlaneSpec spec;
+    int64_t J, R, Jr, off;   // jobs, phases, phase stride, first code / count slot
+  };
+  std::vector<PlaneSet> pl_sets;        // empty: one set (ctx->plane, the rows kernel)
+  DevBuf<pe::PlaneSpec> pl_specs_d;     // multi-set: the sets' specs and {off, J, Jr} on the device
+  DevBuf<int64_t> pl_meta_d;
+  std::vector<int64_t> pl_cnt_row;      // multi-set: count slot -> job row (-1: padding)
+  int64_t pl_counts_n = 0;              // count slots of the planes path
+  DevBuf<uint32_t> planes;
+  DevBuf<uint64_t> plane_jobs;
+  pe::CodeSpec code{};
+  int64_t code_Jp = 0, node_stride = 0;
+  DevBuf<int64_t> code_vals;
+  DevBuf<uint32_t> code_needs, code_jobs, code_x;
+  DevBuf<uint64_t> mask;
+  DevBuf<unsigned long long> counts;
+  HostBuf<unsigned long long> h_counts;
+  // aggregation: segmented batch and outputs in pinned, device-mapped host memory (pe_kernels.h
+  // AggSegHdr); the device-resident arrays below only serve the PE_AGG_DEVICE=1 A/B path
+  HostBuf<uint8_t> a_stage, a_outh;
+  DevBuf<uint8_t> a_dstage;              // large batches: the packed batch DMA'd to the device chunk by chunk
+  hipStream_t a_h2d = nullptr;           // ... on this copy stream (the kernels wait on its events)
+  std::vector<hipEvent_t> a_ev_h2d;
+  HostBuf<int64_t> a_segoff;
+  HostBuf<uint32_t> a_flag;
+  std::vector<hipEvent_t> a_ev;   // large batches: one per chunk (its outputs are copied out when it is done)
+  DevBuf<uint32_t> a_ctr;   // latency launches: blocks done (the last one stores the flag)
+  uint32_t agg_gen = 0;
+  std::vector<std::vector<AggSeg>> agg_segs;   // per planning range, reused across calls (no allocation per call)
+  std::vector<AggSeg> agg_all;                 // all segments in order
+  DevBuf<int32_t> a_jgo, a_mm, a_rep, a_gco, a_mem;
+  DevBuf<int64_t> a_req, a_out;
+  DevBuf<uint8_t> a_fl, a_pres, a_ovf;
+  // 128-bit aggregation (pe_pg_min_resources_wide): the gathered sub-batch, its device copy (inputs then
+  // outputs) and the outputs read back; the jobs that go wide, the per-job wide-input marks and the
+  // int64 pass's copy of the low limbs with those jobs zeroed.  Grow and are reused.
+  HostBuf<uint8_t> aw_stage, aw_outh;
+  DevBuf<uint8_t> aw_dev;
+  std::vector<int64_t> aw_jobs, aw_lo;
+  std::vector<uint8_t> aw_mark;
+  // gang capacity (pe_gang_capacity): the call's distinct shapes and their results (pinned), the device
+  // copies, the per-node-block partials, the dedupe table and each job's shape.  Grow and are reused;
+  // nothing of the staged fit mask is shared.
+  HostBuf<pe::CapShape> cp_hshapes;
+  HostBuf<pe::CapAcc> cp_hout;
+  DevBuf<pe::CapShape> cp_shapes;
+  DevBuf<pe::CapAcc> cp_part, cp_out;
+  std::vector<pe::CapShape> cp_uniq;
+  std::vector<int32_t> cp_tab, cp_of;
+  hipEvent_t cp_ev[2] = {nullptr, nullptr};   // PE_CAP_EVENTS=1: around the call's kernels
+  // gang capacity per domain (pe_gang_capacity_domains; shapes, dedupe and events are cp_*): the device
+  // tables of one chunk of shapes and their pinned copies, the call's distinct (shape, count) picks with
+  // their answers, the pick dedupe table and each job's pick.  Grow and are reused; nothing outlives a call.
+  DevBuf<uint64_t> dm_table;   // per launch of sc shapes: slots u64 [sc][D], then nodes u32 [sc][D]
+  HostBuf<uint64_t> dm_hslots;
+  HostBuf<uint32_t> dm_hnodes;
+  HostBuf<pe::DomPick> dm_hpicks;
+  DevBuf<pe::DomPick> dm_picks;
+  DevBuf<pe::DomSel> dm_sel;
+  HostBuf<pe::DomSel> dm_hsel;
+  std::vector<pe::DomPick> dm_upicks;
+  std::vector<int32_t> dm_ptab, dm_pof;
+  // greedy
+  DevBuf<ReqRec> g_groups;
+  DevBuf<uint64_t> g_cand, g_bound;
+  DevBuf<int32_t> g_cnt;
+  DevBuf<uint8_t> g_out, g_gath;
+  DevBuf<int64_t> g_upd;
+  DevBuf<uint64_t> g_kn;   // scan: node-only score terms K(n) (prep_nodes), refreshed by apply
+  DevBuf<uint32_t> g_lo;   // scan: lo20(r1) / lo24(r3), [2][stride]
+  HostBuf<ReqRec> h_groups, h_groups2;   // h_groups2: the window requests of blob buffer 1 (signalled walk)
+  HostBuf<ReqRec> h_groupsx[2];           // blob buffers 2, 3 (pipeline depth 2, 3)
+  HostBuf<uint8_t> h_outx[2];             // blob buffers 2, 3
+  HostBuf<int64_t> h_updx[2];             // update staging slots 1, 2 (pipeline depth 2, 3)
+  uint32_t walk_gen = 0;                  // generation of the last signalled walk window (never 0)
+  int pin_cpu = -2;                       // greedy thread pinning at world > 1: a CPU of this rank's L3 (-2: not chosen yet)
+  HostBuf<uint8_t> h_out, h_out2, h_own;   // h_out2: the pipelined loop's second blob buffer (h_outx: 3rd, 4th)
+  HostBuf<uint8_t> h_merged;                // host-exchange windows: the device-merged lists
+  HostBuf<uint8_t> h_xg[4];                 // pipelined host exchange: the gathered lists of blob buffer b
+  std::vector<const uint64_t*> x_lists;     // host merge of the gathered lists (exchange thread scratch)
+  std::vector<int32_t> x_ns, x_hd;
+  HostBuf<int64_t> h_upd;
+  // greedy sorted walk (pe_kernels.h WalkIndex; the default window path, greedy_flags bit1 = full scan)
+  bool walk = true;
+  int64_t resort_nodes = 20480;  // re-sort once this many applied updates joined the overlay
+  int64_t w_est = 0;             // updates applied since the last sort (>= overlay size)
+  // two index sets: the walks read ws[w_cur]; the next one is rebuilt on the side stream w_s2
+  // (lowest priority) while the walks go on (walk_resort_async), then taken over (walk_switch)
+  struct WalkSet {
+    DevBuf<uint64_t> sk, rmin;
+    DevBuf<int64_t> sr, rmax;
+    DevBuf<uint32_t> sl, pos, ror, inovl, ovidx, ovlab;
+    DevBuf<int64_t> ovres;
+    DevBuf<uint64_t> ovkn;
+    DevBuf<int32_t> ovl, ovln;
+    void release() {
+      sk.release(); rmin.release(); sr.release(); rmax.release(); sl.release(); pos.release(); ror.release();
+      inovl.release(); ovidx.release(); ovlab.release(); ovres.release(); ovkn.release(); ovl.release(); ovln.release();
+    }
+  } ws[2];
+  int w_cur = 0;
+  bool w_pending = false;        // ws[1 - w_cur] is being rebuilt on w_s2
+  int64_t w_pend_est = 0;        // updates applied since that rebuild's snapshot
+  int64_t w_pend_windows = 0;    // windows launched while that rebuild was pending
+  hipStream_t w_s2 = nullptr;
+  hipEvent_t w_ev_snap = nullptr, w_ev_done = nullptr;
+  DevBuf<uint64_t> w_kin;
+  DevBuf<uint32_t> w_slow;       // saturating nodes of the side-stream rebuild (walk_switch adds them)
+  DevBuf<uint8_t> w_temp;
+  DevBuf<uint32_t> w_flush;   // PE_WALK_FLUSH: 512 MiB rewritten before each walk (cold-cache diagnostics)
+  DevBuf<unsigned long long> w_stat;   // walk counters of the current pe_place_greedy (rounds, overlay)
+  DevBuf<uint64_t> g_xstatus;          // zero-copy exchange: the window's wait status (launch_xwait)
+  pe_stats stats{};
+
+  ~pe_ctx() {
+    (void)hipSetDevice(device);
+    if (comm_abort.joinable()) comm_abort.join();
+    if (stream) (void)hipStreamSynchronize(stream);
+    res0.release(); res.release(); labels.release(); island.release(); n_upd.release();
+    fit_jobs.release(); fit_jobs32.release(); res32.release(); mask.release();
+    code_vals.release(); code_needs.release(); code_jobs.release(); code_x.release(); counts.release(); h_counts.release();
+    planes.release(); plane_jobs.release();
+    lds_spec_d.release(); lds_vals.release(); lds_codes.release(); lds_ranks.release(); lds_aux.release(); lds_slots.release(); lds_rows.release();
+    a_stage.release(); a_outh.release(); a_segoff.release(); a_flag.release(); a_ctr.release();
+    for (hipEvent_t e : a_ev) (void)hipEventDestroy(e);
+    if (a_h2d) (void)hipStreamSynchronize(a_h2d);
+    for (hipEvent_t e : a_ev_h2d) (void)hipEventDestroy(e);
+    if (a_h2d) (void)hipStreamDestroy(a_h2d);
+    a_dstage.release();
+    a_jgo.release(); a_mm.release(); a_rep.release(); a_gco.release(); a_mem.release();
+    a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
+    aw_stage.release(); aw_outh.release(); aw_dev.release();
+    cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
+    dm_table.release(); dm_hslots.release(); dm_hnodes.release(); dm_hpicks.release();
+    dm_picks.release(); dm_sel.release(); dm_hsel.release();
+    for (hipEvent_t e : cp_ev)
+      if (e) (void)hipEventDestroy(e);
+    g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
+    g_upd.release(); g_kn.release(); g_lo.release(); h_groups.release(); h_groups2.release(); h_out.release(); h_out2.release(); h_own.release(); h_merged.release(); h_upd.release();
+    for (auto& x : h_xg) x.release();
+    for (int i = 0; i < 2; ++i) {
+      h_groupsx[i].release();
+      h_outx[i].release();
+      h_updx[i].release();
+    }
+    if (w_s2) (void)hipStreamSynchronize(w_s2);
+    for (auto& x : ws) x.release();
+    w_kin.release(); w_slow.release(); w_temp.release(); w_stat.release(); w_flush.release(); g_xstatus.release();
+    if (w_ev_snap) (void)hipEventDestroy(w_ev_snap);
+    if (w_ev_done) (void)hipEventDestroy(w_ev_done);
+    if (w_s2) (void)hipStreamDestroy(w_s2);
+    if (comm) (void)ncclCommDestroy(comm);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+namespace pe_engine {
+
+// A collective timed out (pe::CollectiveTimeout): abort the communicator without blocking the caller.
+// ncclCommAbort raises the communicator's abort flag, which the stuck collective kernel polls, and then
+// frees its resources (the frees wait for the device work in flight); on its own thread, so the call
+// that timed out returns PE_ERCCL within the bound; pe_destroy joins it.
+inline void rccl_abort(pe_ctx* ctx) {
+  if (!ctx->comm) return;
+  ncclComm_t c = ctx->comm;
+  ctx->comm = nullptr;
+  ctx->comm_aborted = true;
+  const int dev = ctx->device;
+  ctx->comm_abort = std::thread([c, dev] {
+    (void)hipSetDevice(dev);
+    (void)ncclCommAbort(c);
+  });
+}
+
+// Every ABI entry runs its body through here: lock, select device, map exceptions to codes.
+template <class F>
+int guarded(pe_ctx* ctx, F&& body) {
+  if (!ctx) return PE_EINVAL;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  ctx->err.clear();
+  try {
+    hipchk(hipSetDevice(ctx->device), "hipSetDevice");
+    return body();
+  } catch (const PeError& e) {
+    ctx->err = e.msg;
+    return e.code;
+  } catch (const std::bad_alloc&) {
+    ctx->err = "host allocation failed";
+    return PE_ENOMEM;
+  } catch (const pe::CollectiveTimeout& e) {   // an RCCL window's all-gather never completed
+    ctx->err = e.what();
+    rccl_abort(ctx);
+    return PE_ERCCL;
+  } catch (const pe::ExchangeError& e) {   // a zero-copy window's peer lists never arrived
+    ctx->err = e.what();
+    return PE_ERCCL;
+  } catch (const std::runtime_error& e) {   // pe::WindowFeed: a walk group the device never signalled
+    ctx->err = e.what();
+    return PE_EHIP;
+  } catch (...) {
+    ctx->err = "unexpected C++ exception";
+    return PE_EINVAL;
+  }
+}
+
+inline void need_ptr(const void* p, const char* name) {
+  if (!p) raise(PE_EINVAL, std::string(name) + " is NULL");
+}
+
+// (pe_engine.cpp: they validate large arrays on its planning pool)
+void check_req(const int64_t* req, int64_t n, const char* what);
+void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* what);
+
+inline void fill_req(ReqRec& r, const int64_t* q, uint32_t need) {
+  std::memset(&r, 0, sizeof(r));
+  for (int d = 0; d < pe::D; ++d) r.q[d] = q[d];
+  r.need = need;
+}
+
+}  // namespace pe_engine

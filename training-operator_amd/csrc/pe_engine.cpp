@@ -1,4 +1,5 @@
-// libplacement: context, device-resident inventory, C ABI entry points (include/placement.h).
+// libplacement: context, device-resident inventory, C ABI entry points (include/placement.h) -- all but
+// the greedy placement, which is pe_engine_greedy.cpp; the context itself is pe_ctx.h.
 //
 // One context = one process = one GPU = one contiguous shard of the node inventory.  The
 // inventory lives on the device as int64 struct-of-arrays res[4][stride] (+ labels, islands),
@@ -12,7 +13,6 @@
 #include <sched.h>
 
 #include <algorithm>
-#include <deque>
 #include <condition_variable>
 #include <atomic>
 #include <chrono>
@@ -30,216 +30,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pe_ctx.h"
 #include "pe_divmagic.h"
 #include "pe_hostx.h"
 #include "pe_kernels.h"
-#include "pe_merge.h"
 #include "pe_resolver.h"
 #include "placement.h"
 
 namespace {
-
-using pe::ReqRec;
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  // flags: hipExtMallocWithFlags flags (hipDeviceMallocContiguous falls back to a plain hipMalloc
-  // when the driver cannot provide it)
-  hipError_t ensure(size_t count, unsigned flags = 0) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipErrorOutOfMemory;
-    if (flags) {
-      e = hipExtMallocWithFlags((void**)&p, bytes, flags);
-      if (e != hipSuccess) (void)hipGetLastError();
-    }
-    if (e != hipSuccess) e = hipMalloc((void**)&p, bytes);
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
-// Pinned host buffer.  Coherent (fine-grained) ones are also read and written by kernels directly
-// (dev = the device-side address): per-window inputs and the candidate blob skip the copy engines.
-template <class T>
-struct HostBuf {
-  T* p = nullptr;
-  T* dev = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t count, unsigned flags = hipHostMallocDefault) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = dev = nullptr;
-    n = 0;
-    hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T), flags);
-    // zeroed: several of these buffers carry completion flags (signalled groups, the aggregation
-    // flag) that a recycled allocation could otherwise hold from an earlier engine's generations
-    if (e == hipSuccess) std::memset((void*)p, 0, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dev, p, 0);
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = dev = nullptr;
-    n = 0;
-  }
-};
-constexpr unsigned kZeroCopy = hipHostMallocCoherent | hipHostMallocMapped;
-
-// One helper thread that runs a posted task while the caller does other work (pipelined greedy:
-// the next window's launches are issued while the host resolves the current one).  Spin handoff:
-// the wake-up of a sleeping thread would cost about as much as the launches it hides.
-class SpinWorker {
- public:
-  explicit SpinWorker(int device) : th_([this, device] {
-    (void)hipSetDevice(device);   // the current device is per thread
-    loop();
-  }) {}
-  ~SpinWorker() {
-    while (state_.load(std::memory_order_acquire) == 1) _mm_pause();   // a posted task finishes first
-    state_.store(3, std::memory_order_release);
-    th_.join();
-  }
-  void pin(const cpu_set_t& set) { (void)pthread_setaffinity_np(th_.native_handle(), sizeof(set), &set); }
-  void post(std::function<void()> f) {
-    task_ = std::move(f);
-    err_ = nullptr;
-    posted_ = true;
-    state_.store(1, std::memory_order_release);
-  }
-  bool busy() const { return state_.load(std::memory_order_acquire) == 1; }   // a posted task not done yet
-  bool failed() const { return state_.load(std::memory_order_acquire) == 2 && err_ != nullptr; }
-  void wait() {   // rethrows what the task threw; returns at once when nothing is posted
-    if (!posted_) return;
-    posted_ = false;
-    for (int spin = 0; state_.load(std::memory_order_acquire) != 2; ++spin)
-      if (spin < 4096) _mm_pause();
-      else std::this_thread::yield();   // the helper is not running (oversubscribed host)
-    state_.store(0, std::memory_order_relaxed);
-    if (err_) std::rethrow_exception(err_);
-  }
-
- private:
-  void loop() {
-    int idle = 0;
-    for (;;) {
-      const int st = state_.load(std::memory_order_acquire);
-      if (st == 3) return;
-      if (st != 1) {
-        if (++idle < 4096) _mm_pause();
-        else std::this_thread::yield();   // long idle (host resolving): let others run
-        continue;
-      }
-      idle = 0;
-      try {
-        task_();
-      } catch (...) {
-        err_ = std::current_exception();
-      }
-      state_.store(2, std::memory_order_release);
-    }
-  }
-  std::atomic<int> state_{0};
-  bool posted_ = false;   // (the posting thread's own view: a task posted and not waited for yet)
-  std::function<void()> task_;
-  std::exception_ptr err_;
-  std::thread th_;   // last: starts after the members above exist
-};
-
-// A SpinWorker with a queue: post() does not wait for the previous task (up to kCap in flight), the
-// tasks run in order on the thread, wait() waits for all of them.  After a task threw, the rest are
-// skipped and wait() rethrows.  (The host-merged zero-copy exchange: the main thread posts each
-// window's merge as it launches the window, without waiting for the previous merge to finish.)
-class SpinQueue {
- public:
-  static constexpr unsigned kCap = 8;
-  explicit SpinQueue(int device) : th_([this, device] {
-    (void)hipSetDevice(device);
-    loop();
-  }) {}
-  ~SpinQueue() {
-    while (busy()) _mm_pause();
-    stop_.store(true, std::memory_order_release);
-    th_.join();
-  }
-  void pin(const cpu_set_t& set) { (void)pthread_setaffinity_np(th_.native_handle(), sizeof(set), &set); }
-  void post(std::function<void()> f) {
-    const unsigned t = tail_.load(std::memory_order_relaxed);
-    while (t - head_.load(std::memory_order_acquire) >= kCap) _mm_pause();   // full: the oldest first
-    q_[t % kCap] = std::move(f);
-    tail_.store(t + 1, std::memory_order_release);
-  }
-  bool busy() const { return head_.load(std::memory_order_acquire) != tail_.load(std::memory_order_acquire); }
-  bool failed() const { return failed_.load(std::memory_order_acquire); }
-  void wait() {   // every posted task done; rethrows the first error (once)
-    for (int spin = 0; busy(); ++spin)
-      if (spin < 4096) _mm_pause();
-      else std::this_thread::yield();
-    if (failed_.load(std::memory_order_acquire)) {
-      failed_.store(false, std::memory_order_relaxed);
-      std::exception_ptr e = err_;
-      err_ = nullptr;
-      if (e) std::rethrow_exception(e);
-    }
-  }
-
- private:
-  void loop() {
-    int idle = 0;
-    for (;;) {
-      const unsigned h = head_.load(std::memory_order_relaxed);
-      if (h == tail_.load(std::memory_order_acquire)) {
-        if (stop_.load(std::memory_order_acquire)) return;
-        if (++idle < 4096) _mm_pause();
-        else std::this_thread::yield();
-        continue;
-      }
-      idle = 0;
-      if (!failed_.load(std::memory_order_relaxed)) {
-        try {
-          q_[h % kCap]();
-        } catch (...) {
-          err_ = std::current_exception();
-          failed_.store(true, std::memory_order_release);
-        }
-      }
-      q_[h % kCap] = nullptr;
-      head_.store(h + 1, std::memory_order_release);
-    }
-  }
-  std::function<void()> q_[kCap];
-  std::atomic<unsigned> head_{0}, tail_{0};
-  std::atomic<bool> failed_{false}, stop_{false};
-  std::exception_ptr err_;
-  std::thread th_;   // last: starts after the members above exist
-};
-
-
-struct PeError {
-  int code;
-  std::string msg;
-};
-
-[[noreturn]] void raise(int code, const std::string& msg) { throw PeError{code, msg}; }
-
-void hipchk(hipError_t e, const char* what) {
-  if (e != hipSuccess) raise(PE_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-void ncclchk(ncclResult_t r, const char* what) {
-  if (r != ncclSuccess) raise(PE_ERCCL, std::string(what) + ": " + ncclGetErrorString(r));
-}
 
 // Bound of the communicator set-up: PE_RCCL_INIT_TIMEOUT_S seconds (default 120).
 double rccl_init_timeout_ms() {
@@ -285,304 +83,6 @@ ncclComm_t comm_init_bounded(int device, int world, const ncclUniqueId& id, int 
   }
   ncclchk(st->r, "ncclCommInitRank");
   return st->comm;
-}
-
-// Bound of one RCCL window of the greedy: PE_RCCL_TIMEOUT_S seconds (default 60) blocked on a window
-// whose all-gather has not completed (a peer lost mid-batch) -- then the communicator is aborted and
-// the call returns PE_ERCCL.
-double rccl_timeout_s() {
-  const char* e = std::getenv("PE_RCCL_TIMEOUT_S");
-  const double s = e ? std::atof(e) : 60.0;
-  return s > 0 ? s : 60.0;
-}
-
-int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-// pe_config.fit_path_mask bits
-constexpr int kMaxMergers = 7;   // zero-copy exchange: merge helper threads per rank (at most)
-constexpr int PATH_I64 = 1, PATH_I32 = 2, PATH_CODED = 4, PATH_NO_THERM = 8, PATH_PLANES = 16, PATH_PLANES_BLOCKS = 32,
-              PATH_LDS = 64;
-constexpr int PATHS_ALL = PATH_I64 | PATH_I32 | PATH_CODED | PATH_PLANES | PATH_LDS;
-
-// One segment of the packed aggregation batch (pe_kernels.h AggSegHdr).
-struct AggSeg {
-  int64_t j0;
-  int32_t nj, ng, nc;
-  int64_t bytes;
-  bool narrow;            // the request section narrowed (pe_kernels.h agg_seg_layout), shifts in sh
-  uint8_t sh[pe::AGG_MAX_KEYS];
-};
-
-}  // namespace
-
-struct pe_ctx {
-  std::mutex mu;
-  int device = 0;
-  int rank = 0, world = 1;
-  ncclComm_t comm = nullptr;
-  // a greedy window's collective timed out: the communicator was handed to comm_abort (ncclCommAbort
-  // on its own thread -- it returns once the device work it aborts has drained) and every later
-  // sharded call fails with PE_ERCCL; the caller rebuilds the context (e.g. on the host exchange)
-  bool comm_aborted = false;
-  std::thread comm_abort;
-  std::unique_ptr<pe::Resolver> resolver;   // the greedy's host resolver, reset per batch
-  pe_allgather_fn exchange = nullptr;
-  void* exchange_user = nullptr;
-  void* zc_hx = nullptr;   // the shared-memory exchange whose zero-copy use the ranks agreed on (zc_ok)
-  bool zc_ok = false;
-  int topk = 256, window_groups = 112;
-  bool pipeline = true;   // greedy: scan window w+1 while the host resolves window w (greedy_flags bit0 = off)
-  int64_t window_pods = 1024;
-  int64_t max_nodes = 0;
-  std::string gpu_name, err;
-  hipStream_t stream = nullptr;
-  // inventory shard
-  int64_t n_total = 0, begin = 0, end = 0, Ns = 0, stride = 0;
-  bool loaded = false;
-  // host mirror of the GLOBAL inventory (node states by id, and the reset copy): the greedy
-  // windows ship candidate keys only and the resolver reads node states here
-  std::vector<pe::NodeState, pe::HugeAlloc<pe::NodeState>> m_nodes, m_nodes0;   // (2 MiB pages: random reads)
-  DevBuf<int64_t> res0, res;
-  DevBuf<uint32_t> labels;
-  DevBuf<int32_t> island;
-  DevBuf<pe::NodeUpd> n_upd;   // pe_update_nodes staging
-  // fit mask
-  int64_t fit_J = 0, fit_Jp = 0, Wn = 0, Wt = 0;
-  bool fit_uploaded = false;
-  DevBuf<ReqRec> fit_jobs;
-  DevBuf<pe::ReqRec32> fit_jobs32;
-  DevBuf<int32_t> res32;
-  bool fit32 = false;      // batch is exactly representable in 32 bits (see ReqRec32)
-  int fit_shift[pe::D] = {0, 0, 0, 0};
-  int fit_path = 0;        // 0 int64 compare, 1 int32 compare, 2 dictionary-coded, 3 bit planes, 4 LDS digit planes
-  // LDS digit-plane path (pe_kernels.h LdsSpec): spec, node-block geometry, codes, ranks
-  pe::LdsSpec lds{};
-  int lds_W = 4;                          // u32 words per lane per plane: block = 2048 W nodes
-  int lds_shape[4] = {0, 0, 0, 0};        // fields with 4 / 3 / 2 / 1 digit levels (kernel template)
-  int64_t lds_nblk = 0, lds_R = 1, lds_Tpad = 0, lds_npad = 0, lds_pitch = 0;   // pitch in u64 words
-  DevBuf<pe::LdsSpec> lds_spec_d;
-  DevBuf<int64_t> lds_vals;
-  DevBuf<uint16_t> lds_codes;
-  DevBuf<uint32_t> lds_ranks, lds_aux, lds_slots;   // lds_slots: the fit kernel's per-job u32 count slots
-  DevBuf<uint32_t> lds_rows;                         // the job (mask row) of each count slot, ~0 = none
-  int num_cu = 256;
-  int fit_path_mask = PATHS_ALL;   // allowed paths (pe_config.fit_path_mask)
-  pe::PlaneSpec plane{};
-  int64_t pl_nblk = 0;                   // planes path: 8192-node blocks
-  bool pl_rows = true;                   // planes path: row-major sweep kernel (else block-major streams)
-  int64_t pl_R = 1;                      // row-major kernel: job phases of the uploaded batch
-  int64_t pl_pitch = 0;                  // row-major mask pitch in 8192-node blocks (>= pl_nblk)
-  // A batch with more than PL_MAX distinct (dimension, value) pairs is split into plane sets of at
-  // most PL_MAX pairs each (row-major layout only); each set is encoded and swept on its own by
-  // the indexed-row kernel, its jobs' codes carrying their mask rows.
-  struct PlaneSet {
-    pe::PlaneSpec spec;
-    int64_t J, R, Jr, off;   // jobs, phases, phase stride, first code / count slot
-  };
-  std::vector<PlaneSet> pl_sets;        // empty: one set (ctx->plane, the rows kernel)
-  DevBuf<pe::PlaneSpec> pl_specs_d;     // multi-set: the sets' specs and {off, J, Jr} on the device
-  DevBuf<int64_t> pl_meta_d;
-  std::vector<int64_t> pl_cnt_row;      // multi-set: count slot -> job row (-1: padding)
-  int64_t pl_counts_n = 0;              // count slots of the planes path
-  DevBuf<uint32_t> planes;
-  DevBuf<uint64_t> plane_jobs;
-  pe::CodeSpec code{};
-  int64_t code_Jp = 0, node_stride = 0;
-  DevBuf<int64_t> code_vals;
-  DevBuf<uint32_t> code_needs, code_jobs, code_x;
-  DevBuf<uint64_t> mask;
-  DevBuf<unsigned long long> counts;
-  HostBuf<unsigned long long> h_counts;
-  // aggregation: segmented batch and outputs in pinned, device-mapped host memory (pe_kernels.h
-  // AggSegHdr); the device-resident arrays below only serve the PE_AGG_DEVICE=1 A/B path
-  HostBuf<uint8_t> a_stage, a_outh;
-  DevBuf<uint8_t> a_dstage;              // large batches: the packed batch DMA'd to the device chunk by chunk
-  hipStream_t a_h2d = nullptr;           // ... on this copy stream (the kernels wait on its events)
-  std::vector<hipEvent_t> a_ev_h2d;
-  HostBuf<int64_t> a_segoff;
-  HostBuf<uint32_t> a_flag;
-  std::vector<hipEvent_t> a_ev;   // large batches: one per chunk (its outputs are copied out when it is done)
-  DevBuf<uint32_t> a_ctr;   // latency launches: blocks done (the last one stores the flag)
-  uint32_t agg_gen = 0;
-  std::vector<std::vector<AggSeg>> agg_segs;   // per planning range, reused across calls (no allocation per call)
-  std::vector<AggSeg> agg_all;                 // all segments in order
-  DevBuf<int32_t> a_jgo, a_mm, a_rep, a_gco, a_mem;
-  DevBuf<int64_t> a_req, a_out;
-  DevBuf<uint8_t> a_fl, a_pres, a_ovf;
-  // 128-bit aggregation (pe_pg_min_resources_wide): the gathered sub-batch, its device copy (inputs then
-  // outputs) and the outputs read back; the jobs that go wide, the per-job wide-input marks and the
-  // int64 pass's copy of the low limbs with those jobs zeroed.  Grow and are reused.
-  HostBuf<uint8_t> aw_stage, aw_outh;
-  DevBuf<uint8_t> aw_dev;
-  std::vector<int64_t> aw_jobs, aw_lo;
-  std::vector<uint8_t> aw_mark;
-  // gang capacity (pe_gang_capacity): the call's distinct shapes and their results (pinned), the device
-  // copies, the per-node-block partials, the dedupe table and each job's shape.  Grow and are reused;
-  // nothing of the staged fit mask is shared.
-  HostBuf<pe::CapShape> cp_hshapes;
-  HostBuf<pe::CapAcc> cp_hout;
-  DevBuf<pe::CapShape> cp_shapes;
-  DevBuf<pe::CapAcc> cp_part, cp_out;
-  std::vector<pe::CapShape> cp_uniq;
-  std::vector<int32_t> cp_tab, cp_of;
-  hipEvent_t cp_ev[2] = {nullptr, nullptr};   // PE_CAP_EVENTS=1: around the call's kernels
-  // gang capacity per domain (pe_gang_capacity_domains; shapes, dedupe and events are cp_*): the device
-  // tables of one chunk of shapes and their pinned copies, the call's distinct (shape, count) picks with
-  // their answers, the pick dedupe table and each job's pick.  Grow and are reused; nothing outlives a call.
-  DevBuf<uint64_t> dm_table;   // per launch of sc shapes: slots u64 [sc][D], then nodes u32 [sc][D]
-  HostBuf<uint64_t> dm_hslots;
-  HostBuf<uint32_t> dm_hnodes;
-  HostBuf<pe::DomPick> dm_hpicks;
-  DevBuf<pe::DomPick> dm_picks;
-  DevBuf<pe::DomSel> dm_sel;
-  HostBuf<pe::DomSel> dm_hsel;
-  std::vector<pe::DomPick> dm_upicks;
-  std::vector<int32_t> dm_ptab, dm_pof;
-  // greedy
-  DevBuf<ReqRec> g_groups;
-  DevBuf<uint64_t> g_cand, g_bound;
-  DevBuf<int32_t> g_cnt;
-  DevBuf<uint8_t> g_out, g_gath;
-  DevBuf<int64_t> g_upd;
-  DevBuf<uint64_t> g_kn;   // scan: node-only score terms K(n) (prep_nodes), refreshed by apply
-  DevBuf<uint32_t> g_lo;   // scan: lo20(r1) / lo24(r3), [2][stride]
-  HostBuf<ReqRec> h_groups, h_groups2;   // h_groups2: the window requests of blob buffer 1 (signalled walk)
-  HostBuf<ReqRec> h_groupsx[2];           // blob buffers 2, 3 (pipeline depth 2, 3)
-  HostBuf<uint8_t> h_outx[2];             // blob buffers 2, 3
-  HostBuf<int64_t> h_updx[2];             // update staging slots 1, 2 (pipeline depth 2, 3)
-  uint32_t walk_gen = 0;                  // generation of the last signalled walk window (never 0)
-  int pin_cpu = -2;                       // greedy thread pinning at world > 1: a CPU of this rank's L3 (-2: not chosen yet)
-  HostBuf<uint8_t> h_out, h_out2, h_own;   // h_out2: the pipelined loop's second blob buffer (h_outx: 3rd, 4th)
-  HostBuf<uint8_t> h_merged;                // host-exchange windows: the device-merged lists
-  HostBuf<uint8_t> h_xg[4];                 // pipelined host exchange: the gathered lists of blob buffer b
-  std::vector<const uint64_t*> x_lists;     // host merge of the gathered lists (exchange thread scratch)
-  std::vector<int32_t> x_ns, x_hd;
-  HostBuf<int64_t> h_upd;
-  // greedy sorted walk (pe_kernels.h WalkIndex; the default window path, greedy_flags bit1 = full scan)
-  bool walk = true;
-  int64_t resort_nodes = 20480;  // re-sort once this many applied updates joined the overlay
-  int64_t w_est = 0;             // updates applied since the last sort (>= overlay size)
-  // two index sets: the walks read ws[w_cur]; the next one is rebuilt on the side stream w_s2
-  // (lowest priority) while the walks go on (walk_resort_async), then taken over (walk_switch)
-  struct WalkSet {
-    DevBuf<uint64_t> sk, rmin;
-    DevBuf<int64_t> sr, rmax;
-    DevBuf<uint32_t> sl, pos, ror, inovl, ovidx, ovlab;
-    DevBuf<int64_t> ovres;
-    DevBuf<uint64_t> ovkn;
-    DevBuf<int32_t> ovl, ovln;
-    void release() {
-      sk.release(); rmin.release(); sr.release(); rmax.release(); sl.release(); pos.release(); ror.release();
-      inovl.release(); ovidx.release(); ovlab.release(); ovres.release(); ovkn.release(); ovl.release(); ovln.release();
-    }
-  } ws[2];
-  int w_cur = 0;
-  bool w_pending = false;        // ws[1 - w_cur] is being rebuilt on w_s2
-  int64_t w_pend_est = 0;        // updates applied since that rebuild's snapshot
-  int64_t w_pend_windows = 0;    // windows launched while that rebuild was pending
-  hipStream_t w_s2 = nullptr;
-  hipEvent_t w_ev_snap = nullptr, w_ev_done = nullptr;
-  DevBuf<uint64_t> w_kin;
-  DevBuf<uint32_t> w_slow;       // saturating nodes of the side-stream rebuild (walk_switch adds them)
-  DevBuf<uint8_t> w_temp;
-  DevBuf<uint32_t> w_flush;   // PE_WALK_FLUSH: 512 MiB rewritten before each walk (cold-cache diagnostics)
-  DevBuf<unsigned long long> w_stat;   // walk counters of the current pe_place_greedy (rounds, overlay)
-  DevBuf<uint64_t> g_xstatus;          // zero-copy exchange: the window's wait status (launch_xwait)
-  pe_stats stats{};
-
-  ~pe_ctx() {
-    (void)hipSetDevice(device);
-    if (comm_abort.joinable()) comm_abort.join();
-    if (stream) (void)hipStreamSynchronize(stream);
-    res0.release(); res.release(); labels.release(); island.release(); n_upd.release();
-    fit_jobs.release(); fit_jobs32.release(); res32.release(); mask.release();
-    code_vals.release(); code_needs.release(); code_jobs.release(); code_x.release(); counts.release(); h_counts.release();
-    planes.release(); plane_jobs.release();
-    lds_spec_d.release(); lds_vals.release(); lds_codes.release(); lds_ranks.release(); lds_aux.release(); lds_slots.release(); lds_rows.release();
-    a_stage.release(); a_outh.release(); a_segoff.release(); a_flag.release(); a_ctr.release();
-    for (hipEvent_t e : a_ev) (void)hipEventDestroy(e);
-    if (a_h2d) (void)hipStreamSynchronize(a_h2d);
-    for (hipEvent_t e : a_ev_h2d) (void)hipEventDestroy(e);
-    if (a_h2d) (void)hipStreamDestroy(a_h2d);
-    a_dstage.release();
-    a_jgo.release(); a_mm.release(); a_rep.release(); a_gco.release(); a_mem.release();
-    a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
-    aw_stage.release(); aw_outh.release(); aw_dev.release();
-    cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
-    dm_table.release(); dm_hslots.release(); dm_hnodes.release(); dm_hpicks.release();
-    dm_picks.release(); dm_sel.release(); dm_hsel.release();
-    for (hipEvent_t e : cp_ev)
-      if (e) (void)hipEventDestroy(e);
-    g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
-    g_upd.release(); g_kn.release(); g_lo.release(); h_groups.release(); h_groups2.release(); h_out.release(); h_out2.release(); h_own.release(); h_merged.release(); h_upd.release();
-    for (auto& x : h_xg) x.release();
-    for (int i = 0; i < 2; ++i) {
-      h_groupsx[i].release();
-      h_outx[i].release();
-      h_updx[i].release();
-    }
-    if (w_s2) (void)hipStreamSynchronize(w_s2);
-    for (auto& x : ws) x.release();
-    w_kin.release(); w_slow.release(); w_temp.release(); w_stat.release(); w_flush.release(); g_xstatus.release();
-    if (w_ev_snap) (void)hipEventDestroy(w_ev_snap);
-    if (w_ev_done) (void)hipEventDestroy(w_ev_done);
-    if (w_s2) (void)hipStreamDestroy(w_s2);
-    if (comm) (void)ncclCommDestroy(comm);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-namespace {
-
-// A collective timed out (pe::CollectiveTimeout): abort the communicator without blocking the caller.
-// ncclCommAbort raises the communicator's abort flag, which the stuck collective kernel polls, and then
-// frees its resources (the frees wait for the device work in flight); on its own thread, so the call
-// that timed out returns PE_ERCCL within the bound; pe_destroy joins it.
-void rccl_abort(pe_ctx* ctx) {
-  if (!ctx->comm) return;
-  ncclComm_t c = ctx->comm;
-  ctx->comm = nullptr;
-  ctx->comm_aborted = true;
-  const int dev = ctx->device;
-  ctx->comm_abort = std::thread([c, dev] {
-    (void)hipSetDevice(dev);
-    (void)ncclCommAbort(c);
-  });
-}
-
-// Every ABI entry runs its body through here: lock, select device, map exceptions to codes.
-template <class F>
-int guarded(pe_ctx* ctx, F&& body) {
-  if (!ctx) return PE_EINVAL;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  ctx->err.clear();
-  try {
-    hipchk(hipSetDevice(ctx->device), "hipSetDevice");
-    return body();
-  } catch (const PeError& e) {
-    ctx->err = e.msg;
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    ctx->err = "host allocation failed";
-    return PE_ENOMEM;
-  } catch (const pe::CollectiveTimeout& e) {   // an RCCL window's all-gather never completed
-    ctx->err = e.what();
-    rccl_abort(ctx);
-    return PE_ERCCL;
-  } catch (const pe::ExchangeError& e) {   // a zero-copy window's peer lists never arrived
-    ctx->err = e.what();
-    return PE_ERCCL;
-  } catch (const std::runtime_error& e) {   // pe::WindowFeed: a walk group the device never signalled
-    ctx->err = e.what();
-    return PE_EHIP;
-  } catch (...) {
-    ctx->err = "unexpected C++ exception";
-    return PE_EINVAL;
-  }
-}
-
-void need_ptr(const void* p, const char* name) {
-  if (!p) raise(PE_EINVAL, std::string(name) + " is NULL");
 }
 
 // Persistent helpers for the batch planning (pe_jobs_upload is on the batch's path; creating and
@@ -733,6 +233,10 @@ int64_t first_bad(int64_t n, Bad bad) {
   return r;
 }
 
+}  // namespace
+
+namespace pe_engine {
+
 void check_req(const int64_t* req, int64_t n, const char* what) {
   const int64_t i = first_bad(n * pe::D, [req](int64_t k) { return req[k] < 0; });
   if (i < n * pe::D) raise(PE_EINVAL, std::string(what) + ": negative request at index " + std::to_string(i));
@@ -745,6 +249,10 @@ void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* wha
   if (limit >= 0 && off[n] > limit) raise(PE_EINVAL, std::string(what) + " exceeds its array");
 }
 
+}  // namespace pe_engine
+
+namespace {
+
 // body(j0, j1) over [0, n) in contiguous chunks: on up to 8 threads for large batches (the batch
 // planning is on the upload's path), inline for small ones.  Exceptions are rethrown here.
 template <class Body>
@@ -755,12 +263,6 @@ void parallel_for(int64_t n, Body body) {
     return;
   }
   PlanPool::get().run((int)nt, [&](int t) { body(n * t / nt, n * (t + 1) / nt); });
-}
-
-void fill_req(ReqRec& r, const int64_t* q, uint32_t need) {
-  std::memset(&r, 0, sizeof(r));
-  for (int d = 0; d < pe::D; ++d) r.q[d] = q[d];
-  r.need = need;
 }
 
 }  // namespace
@@ -2956,1166 +2458,6 @@ int pe_gang_capacity_domains(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, co
   });
 }
 
-// ------------------------------------------------------------------ greedy placement
-
-// The sorted-walk index of the shard over the current residuals (g_kn must be current): sort the
-// walkable nodes by K(n), gather the sorted SoA copy and the round summaries, empty the overlay
-// (then holding only the saturating nodes).
-static pe::WalkIndex walk_index(pe_ctx* ctx, int set) {
-  pe_ctx::WalkSet& x = ctx->ws[set];
-  pe::WalkIndex w{};
-  w.sk = x.sk.p;
-  w.sr = x.sr.p;
-  w.sl = x.sl.p;
-  w.pos = x.pos.p;
-  w.rmin = x.rmin.p;
-  w.rmax = x.rmax.p;
-  w.ror = x.ror.p;
-  w.ovl = x.ovl.p;
-  w.ovl_n = x.ovln.p;
-  w.in_ovl = x.inovl.p;
-  w.ovl_idx = x.ovidx.p;
-  w.ovl_res = x.ovres.p;
-  w.ovl_lab = x.ovlab.p;
-  w.ovl_kn = x.ovkn.p;
-  w.stat = ctx->w_stat.p;
-  w.sstride = ctx->stride;
-  w.nr = (ctx->Ns + pe::WK_ROUND - 1) / pe::WK_ROUND;
-  return w;
-}
-static pe::WalkIndex walk_index(pe_ctx* ctx) { return walk_index(ctx, ctx->w_cur); }
-
-// Index set `set` allocated and its overlay / pos cleared on stream s; returns the sort scratch size.
-static size_t walk_set_prepare(pe_ctx* ctx, int set, hipStream_t s) {
-  const int64_t Ns = ctx->Ns, st = std::max<int64_t>(ctx->stride, 1);
-  const int64_t nr = std::max<int64_t>(1, (Ns + pe::WK_ROUND - 1) / pe::WK_ROUND);
-  if (nr > pe::WK_MAXR) raise(PE_EINVAL, "shard too large for the sorted walk");
-  pe_ctx::WalkSet& x = ctx->ws[set];
-  hipchk(x.sk.ensure(st), "alloc walk keys");
-  hipchk(ctx->w_kin.ensure(st), "alloc walk keys");
-  hipchk(x.sr.ensure((size_t)pe::D * st), "alloc walk residuals");
-  hipchk(x.sl.ensure(st), "alloc walk labels");
-  hipchk(x.pos.ensure(st), "alloc walk pos");
-  hipchk(x.rmin.ensure(nr), "alloc walk rounds");
-  hipchk(x.rmax.ensure((size_t)pe::D * nr), "alloc walk rounds");
-  hipchk(x.ror.ensure(nr), "alloc walk rounds");
-  hipchk(x.ovl.ensure(st), "alloc overlay");
-  hipchk(x.ovln.ensure(1), "alloc overlay");
-  hipchk(x.inovl.ensure(st), "alloc overlay");
-  hipchk(x.ovidx.ensure(st), "alloc overlay");
-  hipchk(x.ovlab.ensure(st), "alloc overlay");
-  hipchk(x.ovres.ensure((size_t)pe::D * st), "alloc overlay");
-  hipchk(x.ovkn.ensure(st), "alloc overlay");
-  size_t tb = 0;
-  hipchk(pe::sort_keys_u64(nullptr, &tb, ctx->w_kin.p, x.sk.p, Ns, s), "sort size");
-  hipchk(ctx->w_temp.ensure(tb), "alloc sort scratch");
-  hipchk(hipMemsetAsync(x.ovln.p, 0, sizeof(int32_t), s), "memset overlay");
-  hipchk(hipMemsetAsync(x.inovl.p, 0, (size_t)st * 4, s), "memset overlay");
-  hipchk(hipMemsetAsync(x.pos.p, 0xFF, (size_t)st * 4, s), "memset pos");
-  return tb;
-}
-
-// A side-stream rebuild still running is waited for and dropped (the caller rebuilds in line).
-static void walk_drop_pending(pe_ctx* ctx) {
-  if (!ctx->w_pending) return;
-  hipchk(hipStreamSynchronize(ctx->w_s2), "sync walk rebuild");
-  ctx->w_pending = false;
-}
-
-// In-line rebuild of the current set on the main stream (the walks after it wait for it).
-static void walk_resort(pe_ctx* ctx) {
-  walk_drop_pending(ctx);
-  hipStream_t s = ctx->stream;
-  const int64_t Ns = ctx->Ns;
-  size_t tb = walk_set_prepare(ctx, ctx->w_cur, s);
-  const pe::WalkIndex w = walk_index(ctx);
-  hipchk(pe::launch_walk_prep(s, ctx->res.p, ctx->stride, Ns, ctx->g_kn.p, ctx->labels.p, ctx->w_kin.p, w),
-         "launch walk_prep");
-  hipchk(pe::sort_keys_u64(ctx->w_temp.p, &tb, ctx->w_kin.p, w.sk, Ns, s), "sort walk keys");
-  hipchk(pe::launch_walk_build(s, ctx->res.p, ctx->stride, ctx->labels.p, Ns, (uint64_t)ctx->begin, w),
-         "launch walk_build");
-  ctx->w_est = 0;
-  ctx->stats.resorts += 1;
-}
-
-// Rebuild the other set on the side stream from the residuals as of now (the main stream's point
-// `snap`), while the main stream's walks keep using the current set: the applies after `snap`
-// update both overlays (apply_kernel nx), and walk_switch drops their nodes' possibly torn sorted
-// entries from the new set once it is built.  The side stream has the lowest priority, so the
-// walks' blocks are dispatched first.  Correct for the same reason as the in-line rebuild: every
-// node changed after the snapshot is in the new overlay with its current state, every other node's
-// sorted entry and round summaries are exact (a torn entry only widens its round's summary).
-static void walk_resort_async(pe_ctx* ctx) {
-  if (!ctx->w_s2) {
-    int least = 0, greatest = 0;
-    hipchk(hipDeviceGetStreamPriorityRange(&least, &greatest), "stream priorities");
-    hipchk(hipStreamCreateWithPriority(&ctx->w_s2, hipStreamNonBlocking, least), "side stream");
-    hipchk(hipEventCreateWithFlags(&ctx->w_ev_snap, hipEventDisableTiming), "event");
-    hipchk(hipEventCreateWithFlags(&ctx->w_ev_done, hipEventDisableTiming), "event");
-  }
-  hipStream_t s = ctx->stream, s2 = ctx->w_s2;
-  const int nx = 1 - ctx->w_cur;
-  const int64_t Ns = ctx->Ns;
-  size_t tb = walk_set_prepare(ctx, nx, s);   // (cleared on the main stream: before any apply that writes it)
-  hipchk(ctx->w_slow.ensure((size_t)std::max<int64_t>(ctx->stride, 1)), "alloc walk slow flags");
-  hipchk(hipMemsetAsync(ctx->w_slow.p, 0, (size_t)std::max<int64_t>(ctx->stride, 1) * 4, s), "memset slow flags");
-  hipchk(hipEventRecord(ctx->w_ev_snap, s), "event record");
-  hipchk(hipStreamWaitEvent(s2, ctx->w_ev_snap, 0), "stream wait");
-  const pe::WalkIndex w = walk_index(ctx, nx);
-  hipchk(pe::launch_walk_prep(s2, ctx->res.p, ctx->stride, Ns, ctx->g_kn.p, ctx->labels.p, ctx->w_kin.p, w,
-                              ctx->w_slow.p),
-         "launch walk_prep");
-  hipchk(pe::sort_keys_u64(ctx->w_temp.p, &tb, ctx->w_kin.p, w.sk, Ns, s2), "sort walk keys");
-  hipchk(pe::launch_walk_build(s2, ctx->res.p, ctx->stride, ctx->labels.p, Ns, (uint64_t)ctx->begin, w),
-         "launch walk_build");
-  hipchk(hipEventRecord(ctx->w_ev_done, s2), "event record");
-  ctx->w_pending = true;
-  ctx->w_pend_est = 0;
-  ctx->w_pend_windows = 0;
-}
-
-// Take over the side-stream rebuild (the main stream waits for it if it is not done yet).
-static void walk_switch(pe_ctx* ctx) {
-  hipStream_t s = ctx->stream;
-  const int nx = 1 - ctx->w_cur;
-  hipchk(hipStreamWaitEvent(s, ctx->w_ev_done, 0), "stream wait");
-  hipchk(pe::launch_walk_switch(s, ctx->res.p, ctx->stride, ctx->labels.p, ctx->Ns, ctx->w_slow.p, walk_index(ctx, nx)),
-         "launch walk_switch");
-  ctx->w_cur = nx;
-  ctx->w_pending = false;
-  ctx->w_est = ctx->w_pend_est;
-  ctx->stats.resorts += 1;
-}
-
-int pe_place_greedy(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
-                    const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need,
-                    int32_t* out_pod_node, int32_t* out_job_status) {
-  return guarded(ctx, [&]() -> int {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    if (ctx->comm_aborted)
-      raise(PE_ERCCL, "the RCCL communicator was aborted after a window's all-gather timed out; recreate the context");
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
-    if (n_jobs == 0) return PE_OK;
-    need_ptr(job_group_off, "job_group_off");
-    need_ptr(priority, "priority");
-    need_ptr(out_job_status, "out_job_status");
-    check_offsets(job_group_off, n_jobs, -1, "job_group_off");
-    const int64_t G = job_group_off[n_jobs];
-    int64_t P = 0;
-    if (G > 0) {
-      need_ptr(group_count, "group_count");
-      need_ptr(group_req, "group_req");
-      check_req(group_req, G, "group_req");
-      for (int64_t g = 0; g < G; ++g) {
-        if (group_count[g] < 0) raise(PE_EINVAL, "negative group_count");
-        P += group_count[g];
-      }
-    }
-    if (P > 0) need_ptr(out_pod_node, "out_pod_node");
-    std::vector<uint32_t> no_need;
-    if (!group_need) {
-      no_need.assign((size_t)std::max<int64_t>(G, 1), 0u);
-      group_need = no_need.data();
-    }
-    // Device preparation first (asynchronous): it runs while the host builds the resolver.
-    hipchk(ctx->g_kn.ensure((size_t)std::max<int64_t>(ctx->stride, 1)), "alloc node keys");
-    hipchk(ctx->g_lo.ensure((size_t)2 * std::max<int64_t>(ctx->stride, 1)), "alloc node lows");
-    // residuals may have changed since the last call (reset, pe_update_nodes): one pass over the shard
-    hipchk(pe::launch_prep_nodes(ctx->stream, ctx->res.p, ctx->stride, ctx->Ns, (uint64_t)ctx->begin, ctx->g_kn.p,
-                                 ctx->g_lo.p),
-           "launch prep_nodes");
-    const bool walk = ctx->walk && ctx->Ns > 0;
-    // Candidate lists that grow after a rescan (sorted walk): windows start with lists of topk keys;
-    // once a window's lists ran out (a rescan: its groups consumed more list entries than it had --
-    // whole-node gangs, all of a window's groups after the same few nodes), the rest of the batch walks
-    // lists of 2 x topk.  Longer lists cost walk time (cfg3: 0.58 -> 1.25 ms of device wait at 512),
-    // rescans cost a drained pipeline each (cfg4: 41 rescans at 256, none at 384).  The blob capacity
-    // is the grown length from the start.  Sharded runs grow alike on every rank (each resolves every
-    // window identically, so all switch at the same window): over a node's shared-memory segment when
-    // its slots hold the grown stride (the host merge cuts at the window's length), and over RCCL, whose
-    // windows are written, gathered and merged at the window's own list length (rccl_grow: the
-    // all-gather moves k_win keys per group, not the capacity).  The decision depends on nothing a rank
-    // holds alone (its shard may be empty): ctx->walk, the segment, the communicator.
-    // PE_NO_LIST_GROWTH=1 keeps topk throughout on an UNSHARDED context (A/B; read per call) -- a
-    // per-process variable cannot steer sharded ranks, which must agree on the stride.
-    const bool rccl_path = ctx->comm && !ctx->exchange;   // the windows go through ncclAllGather (= !use_exchange below)
-    const bool no_growth = ctx->world == 1 && !ctx->comm && std::getenv("PE_NO_LIST_GROWTH") != nullptr;
-    const int K0 = ctx->topk;
-    const int Kg = std::max(K0, std::min(2 * K0, pe::WK_ROUND - 1));
-    pe_host_exchange* const hx_grow = ctx->world > 1 && pe::hx_is(ctx->exchange)
-                                          ? static_cast<pe_host_exchange*>(ctx->exchange_user) : nullptr;
-    const bool kgrow = ctx->walk && !no_growth &&
-                       ((ctx->world == 1 && !ctx->comm) || rccl_path ||
-                        (hx_grow && (size_t)ctx->window_groups * pe::cand_group_bytes(Kg) <= pe::hx_slot_bytes(hx_grow)));
-    const bool rccl_grow = kgrow && rccl_path;
-    const int K = kgrow ? Kg : K0;   // blob stride (list capacity)
-    int k_win = K0;                  // list length walked (changed only while the helper threads are idle)
-    // PE_ASYNC_RESORT=0: rebuild the walk index in line, on the main stream (A/B; read per call).
-    // Otherwise the rebuild starts kResortEarly updates before the threshold on the side stream and
-    // is taken over once done -- or waited for past kResortLate updates over the threshold.
-    const bool async_resort = walk && !(std::getenv("PE_ASYNC_RESORT") && std::atoi(std::getenv("PE_ASYNC_RESORT")) == 0);
-    const int64_t kResortEarly = std::min<int64_t>(4096, ctx->resort_nodes / 4);
-    const int64_t kResortLate = std::max<int64_t>(1, ctx->resort_nodes / 2);
-    const int64_t switch_delay = std::getenv("PE_WALK_SWITCH_DELAY") ? std::atoll(std::getenv("PE_WALK_SWITCH_DELAY")) : 0;
-    hipchk(ctx->w_stat.ensure(2), "alloc walk counters");
-    hipchk(hipMemsetAsync(ctx->w_stat.p, 0, 2 * sizeof(unsigned long long), ctx->stream), "memset walk counters");
-    if (walk) walk_resort(ctx);
-    const auto t_prep = std::chrono::steady_clock::now();
-    // one resolver per context, reset per batch (its arrays and seed helper thread are reused)
-    if (ctx->resolver) ctx->resolver->reset(n_jobs, job_group_off, priority, group_count, group_req, group_need);
-    else ctx->resolver.reset(new pe::Resolver(n_jobs, job_group_off, priority, group_count, group_req, group_need));
-    pe::Resolver& R = *ctx->resolver;
-    R.set_mirror(pe::Mirror{ctx->m_nodes.data(), ctx->n_total});
-    const auto t_res = std::chrono::steady_clock::now();
-    // PE_DUMP_WINDOWS=<file>: record the batch and every window's groups + blob (host resolver
-    // replay, tools/replay_resolver.cc); diagnostics only
-    FILE* dump = nullptr;
-    if (const char* dp = std::getenv("PE_DUMP_WINDOWS")) {
-      dump = std::fopen(dp, "wb");
-      if (dump) {
-        const int64_t hdr[3] = {n_jobs, G, (int64_t)K};   // (the blob stride)
-        std::fwrite(hdr, 8, 3, dump);
-        std::fwrite(job_group_off, 4, (size_t)n_jobs + 1, dump);
-        std::fwrite(priority, 4, (size_t)n_jobs, dump);
-        std::fwrite(group_count, 4, (size_t)G, dump);
-        std::fwrite(group_req, 8, (size_t)G * pe::D, dump);
-        std::fwrite(group_need, 4, (size_t)G, dump);
-        std::fwrite(&ctx->n_total, 8, 1, dump);   // the host mirror at the batch start
-        std::fwrite(ctx->m_nodes.data(), sizeof(pe::NodeState), ctx->m_nodes.size(), dump);
-      }
-    }
-    struct DumpClose { FILE*& f; ~DumpClose() { if (f) std::fclose(f); } } dump_close{dump};
-    // PE_GREEDY_TRACE=1: per-window wait / resolve / post times, summarised on stderr (diagnostics)
-    const bool trace = std::getenv("PE_GREEDY_TRACE") != nullptr;
-    std::vector<double> tr_wait, tr_res, tr_post, tr_xspin, tr_xmerge, tr_xblock;
-    int helper_cpu = -1;
-    struct TraceOut {
-      int& helper_cpu;
-      const bool& on;
-      std::vector<double>& a; std::vector<double>& b; std::vector<double>& c;
-      std::vector<double>& d; std::vector<double>& e; std::vector<double>& f;
-      ~TraceOut() {
-        if (!on || a.empty()) return;
-        auto pr = [](const char* n, std::vector<double>& v) {
-          if (v.empty()) return;
-          std::sort(v.begin(), v.end());
-          double sum = 0;
-          for (double x : v) sum += x;
-          std::fprintf(stderr, "%s n %zu sum %.2f ms mean %.1f us p10 %.1f p50 %.1f p90 %.1f max %.1f\n", n, v.size(),
-                       sum / 1e3, sum / v.size(), v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10], v.back());
-        };
-        pr("wait   ", a);
-        pr("resolve", b);
-        pr("post   ", c);
-        pr("xspin  ", d);   // exchange thread: waiting for the ranks' signals, per window
-        pr("xmerge ", e);   // exchange thread: merging, per window
-        pr("xblock ", f);   // main thread: waiting for the exchange thread before posting
-        auto sib = [](int cpu) {
-          char path[128], buf[64] = {0};
-          std::snprintf(path, sizeof path, "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", cpu);
-          FILE* f = std::fopen(path, "r");
-          if (f) {
-            if (!std::fgets(buf, sizeof buf, f)) buf[0] = 0;
-            std::fclose(f);
-          }
-          buf[std::strcspn(buf, "\n")] = 0;
-          return std::string(buf);
-        };
-        const int mc = sched_getcpu();
-        std::fprintf(stderr, "cpus: main %d (siblings %s) helper %d (siblings %s)\n", mc, sib(mc).c_str(), helper_cpu,
-                     helper_cpu >= 0 ? sib(helper_cpu).c_str() : "-");
-      }
-    } trace_out{helper_cpu, trace, tr_wait, tr_res, tr_post, tr_xspin, tr_xmerge, tr_xblock};
-    int64_t dump_left = std::getenv("PE_DUMP_MAX_WINDOWS") ? std::atoll(std::getenv("PE_DUMP_MAX_WINDOWS")) : INT64_MAX;
-    const size_t gb = pe::cand_group_bytes(K);
-    const int Wmax = ctx->window_groups;
-    const int Wpad = (int)round_up(Wmax, pe::SC_GT);
-    const int nwaves = (int)std::max<int64_t>(1, (ctx->Ns + pe::SC_SPAN - 1) / pe::SC_SPAN);
-    hipchk(ctx->g_groups.ensure(Wpad), "alloc groups");
-    hipchk(ctx->h_groups.ensure(Wpad, kZeroCopy), "alloc pinned groups");
-    hipchk(ctx->g_cand.ensure((size_t)Wpad * nwaves * 64), "alloc cand");
-    hipchk(ctx->g_cnt.ensure((size_t)Wpad * nwaves), "alloc cnt");
-    hipchk(ctx->g_bound.ensure((size_t)Wpad * nwaves), "alloc bound");
-    hipchk(ctx->g_out.ensure((size_t)Wmax * gb), "alloc out");
-    hipchk(ctx->h_out.ensure((size_t)Wmax * gb * ctx->world, kZeroCopy), "alloc pinned out");
-    if (ctx->pipeline) hipchk(ctx->h_out2.ensure((size_t)Wmax * gb * ctx->world, kZeroCopy), "alloc pinned out");
-    if (ctx->world > 1 || ctx->comm) {
-      hipchk(ctx->g_gath.ensure((size_t)Wmax * gb * ctx->world), "alloc gather");
-      hipchk(ctx->h_own.ensure((size_t)Wmax * gb, kZeroCopy), "alloc pinned own");
-    }
-    // PE_WALK_EVENTS=1: hipEvents around every walk launch, summed into stats.walk_ms (diagnostics:
-    // the greedy roofline of bench.py; the events cost a few us of host time per window)
-    const bool wev = walk && std::getenv("PE_WALK_EVENTS") != nullptr;
-    // PE_WALK_FLUSH=1 (diagnostics, with PE_WALK_EVENTS: the COLD-cache greedy roofline): before every
-    // walk launch a 512 MiB device buffer is rewritten, evicting the walk index (sorted keys, residual
-    // copy, round summaries: ~50 MB at 1M nodes) from L2 and the 256 MiB Infinity Cache, so the walk
-    // reads come from HBM.  The fill is outside the walk's events.
-    const bool wflush = walk && std::getenv("PE_WALK_FLUSH") != nullptr;
-    if (wflush) hipchk(ctx->w_flush.ensure((size_t)512 << 20), "alloc flush buffer");
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> walk_events;
-    struct EventsFree {
-      std::vector<std::pair<hipEvent_t, hipEvent_t>>& v;
-      ~EventsFree() {
-        for (auto& p : v) {
-          (void)hipEventDestroy(p.first);
-          (void)hipEventDestroy(p.second);
-        }
-      }
-    } events_free{walk_events};
-    int64_t walk_launch_groups = 0;
-    std::vector<pe::GroupCands> cands;
-    hipStream_t s = ctx->stream;
-    const bool use_exchange = ctx->exchange && !(ctx->world == 1 && !ctx->comm);
-    // The host exchange is a synchronous callback.  Pipelined, the launch helper runs it: after it
-    // issued window w+1's scan it waits for the own lists, exchanges them and launches the device
-    // merge, signalled per group like an RCCL window -- all while the host resolves window w.
-    const bool pipelined = ctx->pipeline;
-    // ---- one window on the device: group requests H2D, scan, merge, (RCCL all-gather), blob D2H
-    int cb = 0;   // the blob buffer of the window being resolved
-    std::unique_ptr<SpinWorker> worker;
-    // The resolver, the seed scorer (pe_resolver.cpp) and the launch helper hand cache lines to each
-    // other every window / group: keep the three on the CPUs that share this thread's L3 (one CCD)
-    // for the call -- intersected with the caller's affinity, restored on return; PE_NO_PIN=1 skips.
-    // With several ranks on one host (world > 1), rank r takes the (r mod n)-th of the n L3 domains
-    // its affinity allows, so ranks do not pile their spinning threads onto one CCD.
-    struct Pin {
-      cpu_set_t old_set, l3;
-      bool on = false;
-      Pin(int rank, int world, int& picked) {
-        if (std::getenv("PE_NO_PIN") || pthread_getaffinity_np(pthread_self(), sizeof(old_set), &old_set) != 0)
-          return;
-        if (world > 1 && picked == -2) picked = pe::l3_pick(old_set, rank);   // sysfs walk once per context
-        const int cpu = world > 1 ? picked : sched_getcpu();
-        if (!pe::l3_cpus(cpu, &l3)) return;
-        CPU_AND(&l3, &l3, &old_set);
-        on = CPU_COUNT(&l3) >= 3 && pthread_setaffinity_np(pthread_self(), sizeof(l3), &l3) == 0;
-      }
-      ~Pin() {
-        if (on) (void)pthread_setaffinity_np(pthread_self(), sizeof(old_set), &old_set);
-      }
-    } pin(ctx->rank, ctx->world, ctx->pin_cpu);
-    if (pipelined) {
-      worker.reset(new SpinWorker(ctx->device));
-      if (pin.on) worker->pin(pin.l3);
-    }
-    if (pin.on) R.pin_helper(pin.l3);
-    // blob buffer b (0: h_out, 1: h_out2, 2-3: h_outx): the windows scanned ahead land in their own
-    // buffers while the host still resolves from the current one's
-    auto outbuf = [&](int b) { return b == 0 ? ctx->h_out.p : b == 1 ? ctx->h_out2.p : ctx->h_outx[b - 2].p; };
-    auto outbufdev = [&](int b) { return b == 0 ? ctx->h_out.dev : b == 1 ? ctx->h_out2.dev : ctx->h_outx[b - 2].dev; };
-    const bool direct_out = ctx->world == 1 && !ctx->comm;
-    // Pipelined walk windows written in place are SIGNALLED per group (pe::WindowFeed): the host
-    // takes each group's list when its block is done, not at a stream sync after the slowest block.
-    // The window requests are then double-buffered like the blobs (a walk may still be running when
-    // the next window's requests are written); seeing any group of window w signalled proves that
-    // every earlier launch of the stream is complete (kernels of one stream run in order), which is
-    // what the pinned update records need.  PE_NO_GROUP_SIGNAL=1: stream sync per window instead.
-    // Multi-rank windows (RCCL all-gather, or the host exchange): the gathered shard lists are merged
-    // on the device into one list per group (merge_shards), written into pinned host memory and
-    // signalled like an unsharded walk window -- no D2H of every shard's lists, no host k-way merge.
-    // PE_HOST_MERGE=1: the gathered blob is copied and merged lazily on the host instead.
-    // (PE_HOST_MERGE=1 with a host exchange, measured: the lazy host merge doubled the resolve --
-    // the seed helper cannot pre-skip merged lists -- 20.4 vs 8.9 ms per 2-rank cfg3 batch)
-    // (merge_shards_kernel stages one header per rank in a wave's lanes: world <= MG_THREADS / 64;
-    // wider sharded runs take the host merge)
-    const bool dev_merge = !direct_out && (int64_t)ctx->world * K <= pe::MG_CAP &&
-                           ctx->world <= pe::MG_THREADS / 64 && !std::getenv("PE_HOST_MERGE");
-    // the shard merge kernel: at 1-2 ranks the rank merge (256-thread blocks, a cut of each list ranked,
-    // no sort), from 3 ranks the top-K sort merge (1024-thread blocks) -- measured alone on one MI355X,
-    // 112 groups of K = 256 (tools/bench_merge_dev.cc, profiles/r23_merge_dev.txt): rank 13.7 / 19.9 /
-    // 35.0 / 102 us per window at 2 / 4 / 8 / 16 ranks, sort 18.0 / 14.8 / 15.2 / 19.3 us.
-    // PE_MERGE_RANKED=1 / PE_MERGE_SORT=1 force one (A/B; the rank merge only where its LDS holds the lists).
-    const bool ranked = (std::getenv("PE_MERGE_RANKED") || (ctx->world <= 2 && !std::getenv("PE_MERGE_SORT"))) &&
-                        ctx->world <= pe::RM_MAX_WORLD && pe::merge_ranked_lds(ctx->world, K) <= pe::RM_MAX_LDS;
-    auto* const merge_fn = ranked ? &pe::launch_merge_ranked : &pe::launch_merge_shards;
-    const bool signalled = pipelined && !std::getenv("PE_NO_GROUP_SIGNAL") && (direct_out ? walk : dev_merge);
-    // Zero-copy shared-memory exchange (pe_hostx.h): decided first, the pipeline depth depends on it.
-    bool zc = false;
-    pe_host_exchange* const hx = pe::hx_is(ctx->exchange) ? static_cast<pe_host_exchange*>(ctx->exchange_user) : nullptr;
-    if (hx && use_exchange && pipelined && signalled && ctx->walk && !std::getenv("PE_NO_ZC_EXCHANGE")) {
-      if (ctx->zc_hx != hx) {
-        const uint8_t ok = ctx->world <= pe::HX_ZC_MAX_WORLD && pe::hx_zc_register(hx) &&
-                                   (size_t)Wmax * gb <= pe::hx_slot_bytes(hx) ? 1 : 0;
-        std::vector<uint8_t> all((size_t)ctx->world, 0);
-        if (ctx->exchange(ctx->exchange_user, &ok, all.data(), 1) != 0) raise(PE_ERCCL, "exchange callback failed");
-        ctx->zc_ok = std::all_of(all.begin(), all.end(), [](uint8_t v) { return v == 1; });
-        ctx->zc_hx = hx;
-      }
-      zc = ctx->zc_ok;
-      if (zc) hipchk(ctx->g_xstatus.ensure(1), "alloc exchange status");
-    }
-    // Pipeline depth D (signalled windows; PE_PIPE_DEPTH, 1..3, default 1): windows i+1 .. i+D are
-    // scanned while window i is resolved (D + 1 blob / request buffers, D update staging slots).  (2
-    // measured on a 2-rank host-exchange run: 36 vs 22 ms per cfg3 batch -- every dropped speculation
-    // throws away two scans.)
-    // A copying split exchange (below) reads this rank's lists from the one h_own buffer while the
-    // walk of the next window would overwrite it: depth 1 there (only zero-copy windows go deeper).
-    const bool copy_split = use_exchange && walk && !zc;
-    const int depth = !pipelined ? 0 : !signalled || copy_split ? 1 : [&] {
-      const char* e = std::getenv("PE_PIPE_DEPTH");
-      return e ? std::min(3, std::max(1, std::atoi(e))) : 1;
-    }();
-    if (signalled) hipchk(ctx->h_groups2.ensure(Wpad, kZeroCopy), "alloc pinned groups");
-    for (int b = 2; b <= depth; ++b) {
-      hipchk(ctx->h_groupsx[b - 2].ensure(Wpad, kZeroCopy), "alloc pinned groups");
-      hipchk(ctx->h_outx[b - 2].ensure((size_t)Wmax * gb * ctx->world, kZeroCopy), "alloc pinned out");
-    }
-    auto hgroups = [&](int b) -> HostBuf<ReqRec>& {
-      return !signalled || b == 0 ? ctx->h_groups : b == 1 ? ctx->h_groups2 : ctx->h_groupsx[b - 2];
-    };
-    if (dev_merge && use_exchange && !pipelined)
-      hipchk(ctx->h_merged.ensure((size_t)Wmax * gb, kZeroCopy), "alloc pinned merged");
-    if (dev_merge && use_exchange && pipelined)
-      for (int b = 0; b <= std::max(depth, 1); ++b)
-        hipchk(ctx->h_xg[b].ensure((size_t)Wmax * gb * ctx->world, kZeroCopy), "alloc pinned gathered");
-    const uint8_t* last_blob = nullptr;   // the parsed blob of the window being resolved (one list per group
-                                          // unless the shards are merged on the host)
-    uint32_t buf_gen[4] = {0, 0, 0, 0};
-    int buf_k[4] = {K, K, K, K};   // the list stride each blob buffer's window was written with
-    pe::WindowFeed feed;
-    struct StreamIdle {
-      hipStream_t s;
-      const SpinQueue* x = nullptr;   // the exchange thread (split exchange): a merge it has not launched yet
-      // a faulted walk / merge kernel surfaces as its own HIP error (PE_EHIP with the HIP string),
-      // and a failed exchange as its own error, not as the feed's "never signalled"
-      static bool stream_busy(hipStream_t s) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e == hipErrorNotReady) return true;
-        hipchk(e, "walk window stream");
-        return false;
-      }
-      static bool busy(void* u) {
-        auto* t = static_cast<StreamIdle*>(u);
-        if (t->x && t->x->failed()) const_cast<SpinQueue*>(t->x)->wait();   // rethrows the exchange's error
-        return (t->x && t->x->busy()) || stream_busy(t->s);
-      }
-    } stream_idle{s};
-    feed.idle = &StreamIdle::busy;
-    feed.idle_user = &stream_idle;
-    // RCCL transport: every wait for the stream is bounded (PE_RCCL_TIMEOUT_S) -- a collective that
-    // never completes keeps the stream busy, which the idle test above cannot tell from a slow walk
-    const double coll_tmo = !use_exchange && ctx->comm ? rccl_timeout_s() : 0.0;
-    feed.timeout_s = coll_tmo;
-    // a timed-out window starts the communicator's abort where it is detected, before the unwinding
-    // (the launch helper's and the events' clean-up) could wait on anything the stuck collective holds
-    feed.on_timeout = [](void* u) { rccl_abort(static_cast<pe_ctx*>(u)); };
-    feed.timeout_user = ctx;
-    auto sync_stream = [&](const char* what) {
-      if (coll_tmo <= 0) return hipchk(hipStreamSynchronize(s), what);
-      const auto ts = std::chrono::steady_clock::now();
-      for (unsigned spin = 1;; ++spin) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e != hipErrorNotReady) return hipchk(e, what);
-        if (spin > 64) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        if ((spin & 63) == 0 &&
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count() > coll_tmo) {
-          rccl_abort(ctx);   // (at the throw site: see feed.on_timeout)
-          throw pe::CollectiveTimeout(std::string(what) + ": the stream did not drain within " +
-                                      std::to_string(coll_tmo) +
-                                      " s -- a window's all-gather is stuck (a peer stalled or was lost; PE_RCCL_TIMEOUT_S)");
-        }
-      }
-    };
-    // PE_TEST_STALL_WINDOW=n, PE_TEST_STALL_MS=m (test knob, RCCL transport): a one-thread kernel that
-    // holds the stream for m ms (wall clock, bounded) is queued right before window n's all-gather --
-    // a stand-in for a collective whose peer is gone
-    const int64_t stall_window = std::getenv("PE_TEST_STALL_WINDOW") ? std::atoll(std::getenv("PE_TEST_STALL_WINDOW")) : -1;
-    const int64_t stall_ticks = [] {
-      const char* e = std::getenv("PE_TEST_STALL_MS");
-      const double ms = e ? std::atof(e) : 0.0;
-      return (int64_t)(std::min(std::max(ms, 0.0), 30000.0) * 1e5);   // wall_clock64: 100 MHz; at most 30 s
-    }();
-    double feed_spin_seen = 0;   // feed.spin_ms() already counted as device wait
-    // A pipelined host exchange with device merge runs on its own thread (split_x): the launch helper
-    // only launches window w+1's walk (its lists signalled into pinned memory), the exchange thread
-    // waits for them, exchanges and launches the device merge, while the host resolves window w --
-    // the resolver then waits for the merged groups' signals only, not for the whole chain.
-    // Zero-copy shared-memory exchange (pe_hostx.h): each window's walk writes this rank's lists into
-    // its slot of the registered segment and the shard merge, queued behind it, waits on the device
-    // for every rank's signal of its group -- no exchange thread, no host barrier, no copies.  The
-    // ranks agree on it once per context and segment (each says whether it could register the
-    // segment); PE_NO_ZC_EXCHANGE=1 (every rank): the copying exchange below.  (zc is set above.)
-    // a rank whose peer stalls: its wait gives up after PE_HX_GPU_TIMEOUT_S (default 60) and the
-    // resolver raises (the merged lists come back with n = -1), the GPU is not held
-    const int64_t zc_ticks = [] {
-      const char* e = std::getenv("PE_HX_GPU_TIMEOUT_S");
-      const double t = e ? std::atof(e) : 60.0;
-      return (int64_t)((t > 0 ? t : 60.0) * 1e8);   // wall_clock64: 100 MHz
-    }();
-    // Merging a zero-copy window: by default on the host, by the exchange thread, group by group as
-    // every rank's walk signals it into the segment (zc_host: no kernel, no PCIe read-back, the
-    // resolver streams the merged groups as in an unsharded window); PE_ZC_DEV_MERGE=1 (A/B): a
-    // one-block device wait and the merge kernel behind the walk (zc_dev).
-    const bool zc_dev = zc && std::getenv("PE_ZC_DEV_MERGE");
-    const bool zc_host = zc && !zc_dev;
-    const bool split_x =
-        use_exchange && pipelined && signalled && walk && !zc_dev && !std::getenv("PE_NO_SPLIT_EXCHANGE");
-    std::unique_ptr<SpinQueue> xworker;
-    // Zero-copy windows of 3+ ranks: the exchange thread's host merge grows with the world (8 ranks:
-    // ~1-2 us per group against ~0.5 us of resolve; tools/bench_merge.cc), so the window's groups are
-    // shared among the exchange thread and helpers, group w on thread w mod T (T = 1 + helpers: 2 up to
-    // 4 ranks, 4 above; PE_XCHG_THREADS overrides).  The resolver still takes the groups in order.
-    std::vector<std::unique_ptr<SpinWorker>> xmergers;
-    if (split_x) {
-      xworker.reset(new SpinQueue(ctx->device));
-      if (pin.on) xworker->pin(pin.l3);
-      stream_idle.x = xworker.get();
-      if (zc && !std::getenv("PE_ZC_DEV_MERGE")) {
-        int T = ctx->world <= 2 ? 1 : ctx->world <= 4 ? 2 : 4;
-        if (const char* e = std::getenv("PE_XCHG_THREADS")) T = std::atoi(e);
-        T = std::max(1, std::min(T, kMaxMergers + 1));
-        for (int t = 1; t < T; ++t) {
-          xmergers.emplace_back(new SpinWorker(ctx->device));
-          if (pin.on) xmergers.back()->pin(pin.l3);
-          xmergers.back()->post(&pe::merge_warm);   // (waited for before the first window's share)
-        }
-        xworker->post(&pe::merge_warm);
-      }
-    }
-    struct XWait {   // every exit: the exchange thread's task is over before the buffers it uses go
-      std::unique_ptr<SpinQueue>& w;
-      ~XWait() {
-        if (w) try {
-            w->wait();
-          } catch (...) {
-          }
-      }
-    } xwait_exit{xworker};
-    // PE_XCHG_HOST_MERGE=1 (A/B): the exchange thread merges the gathered lists on the host, group by
-    // group, each signalled as written, instead of the device merge -- measured 36.7 vs 18.5 ms per
-    // 2-rank cfg3 batch (the merge of world x K keys per group is host work the resolver waits on).
-    // The rule is merge_shards_kernel's: the keys below the smallest shard limit, the K + 1 smallest
-    // of them; limit = the (K+1)-th, else that minimum.
-    const bool xhost_merge = use_exchange && dev_merge && std::getenv("PE_XCHG_HOST_MERGE");
-    // merge_shards_kernel's rule on the host: the keys below the smallest shard limit, the K + 1
-    // smallest of them (two shards: a branch-free two-way merge); group w of shard r at
-    // gath + r * stride + w * gb
-    auto host_merge_zc = [&](const uint8_t* gath, size_t stride, int w, uint8_t* out, uint32_t gen) {
-      const int W = ctx->world;
-      const int Kc = k_win;   // the merged list's length: the window's (the stride may be longer)
-      uint8_t* og = out + (size_t)w * gb;
-      uint64_t* dst = reinterpret_cast<uint64_t*>(og + sizeof(pe::CandHdr));
-      uint64_t L = pe::NO_KEY;
-      static_assert(pe::HX_ZC_MAX_WORLD >= pe::RM_MAX_WORLD, "zero-copy merge arrays");
-      const uint64_t* lists[pe::HX_ZC_MAX_WORLD];   // (zero-copy windows: world <= HX_ZC_MAX_WORLD)
-      int ns[pe::HX_ZC_MAX_WORLD];
-      bool bad = false;
-      for (int r = 0; r < W; ++r) {
-        const uint8_t* g = gath + (size_t)r * stride + (size_t)w * gb;
-        pe::CandHdr h;
-        std::memcpy(&h, g, sizeof(h));
-        L = std::min(L, h.limit);
-        lists[r] = reinterpret_cast<const uint64_t*>(g + sizeof(h));
-        bad |= h.n < 0 || h.n > K;   // a corrupt rank list: the merged group says so (never read past it)
-        ns[r] = std::max(0, std::min(h.n, K));
-      }
-      uint64_t lim = L;
-      const int m = bad ? pe::CAND_CORRUPT : pe::merge_rank_lists(lists, ns, W, L, Kc, dst, &lim);
-      pe::CandHdr* hp = reinterpret_cast<pe::CandHdr*>(og);
-      hp->n = m;
-      hp->limit = bad ? 0 : lim;
-      __atomic_store_n(&hp->flags, (int32_t)gen, __ATOMIC_RELEASE);   // the group's signal, last
-    };
-    auto host_merge_group = [&](const uint8_t* gath, int Wg, int w, uint8_t* out, uint32_t gen) {
-      const int W = ctx->world;
-      std::vector<const uint64_t*>& lists = ctx->x_lists;
-      std::vector<int32_t>& ns = ctx->x_ns;
-      std::vector<int32_t>& hd = ctx->x_hd;
-      lists.resize((size_t)W);
-      ns.resize((size_t)W);
-      hd.assign((size_t)W, 0);
-      uint64_t L = pe::NO_KEY;
-      bool bad = false;
-      for (int r = 0; r < W; ++r) {
-        const uint8_t* g = gath + ((size_t)r * Wg + w) * gb;
-        pe::CandHdr h;
-        std::memcpy(&h, g, sizeof(h));
-        L = std::min(L, h.limit);
-        lists[(size_t)r] = reinterpret_cast<const uint64_t*>(g + sizeof(h));
-        bad |= h.n < 0 || h.n > K;   // a corrupt rank list: no key is taken, the group is marked below
-        ns[(size_t)r] = std::max(0, std::min(h.n, K));
-      }
-      uint8_t* og = out + (size_t)w * gb;
-      uint64_t* dst = reinterpret_cast<uint64_t*>(og + sizeof(pe::CandHdr));
-      int m = bad ? pe::CAND_CORRUPT : 0;
-      uint64_t lim = L;
-      for (; !bad;) {
-        int br = -1;
-        uint64_t bk = L;   // (only keys below the smallest limit count)
-        for (int r = 0; r < W; ++r)
-          if (hd[(size_t)r] < ns[(size_t)r] && lists[(size_t)r][hd[(size_t)r]] < bk) {
-            bk = lists[(size_t)r][hd[(size_t)r]];
-            br = r;
-          }
-        if (br < 0) break;
-        if (m == K) {   // a (K+1)-th key below the limit: it is the list's limit
-          lim = bk;
-          break;
-        }
-        dst[m++] = bk;
-        ++hd[(size_t)br];
-      }
-      pe::CandHdr* hp = reinterpret_cast<pe::CandHdr*>(og);
-      hp->n = m;
-      hp->limit = lim;
-      __atomic_store_n(&hp->flags, (int32_t)gen, __ATOMIC_RELEASE);   // the group's signal, last
-    };
-    auto exchange_window = [&](int b, int Wg, uint32_t gen, bool own_direct, const SpinWorker* launcher,
-                               const pe::HxWindow* hw = nullptr) {
-      const size_t bytes = (size_t)Wg * gb;
-      if (zc_host) {   // every rank's lists are in the segment: merge each group as all ranks signalled it
-        const double tmo = pe::hx_timeout_s();
-        const auto t0 = std::chrono::steady_clock::now();
-        const int T = 1 + (int)xmergers.size();   // the exchange thread + its merge helpers, groups w = t mod T
-        const size_t pf_bytes = pe::merge_read_bytes(ctx->world, k_win, gb);
-        // one share of the window: groups t, t + T, ... (waited / merged / spun: this share's times)
-        auto share = [&, hw, b, gen, Wg](int t, double* waited, double* spun, double* merged) {
-          for (int w = t; w < Wg; w += T) {
-            const auto ts = trace ? std::chrono::steady_clock::now() : t0;
-            for (int r = 0; r < ctx->world; ++r) {
-              const pe::CandHdr* h = reinterpret_cast<const pe::CandHdr*>(hw->host + (size_t)r * hw->slot + (size_t)w * gb);
-              if (__atomic_load_n(&h->flags, __ATOMIC_ACQUIRE) == (int32_t)hw->gen) continue;
-              const auto tw = std::chrono::steady_clock::now();
-              for (unsigned spin = 1; __atomic_load_n(&h->flags, __ATOMIC_ACQUIRE) != (int32_t)hw->gen; ++spin) {
-                _mm_pause();
-                if ((spin & 4095) == 0) {
-                  if (t == 0) {   // (HIP calls from the exchange thread only) a faulted walk of this rank: its own error
-                    const hipError_t e = hipStreamQuery(s);
-                    if (e != hipErrorNotReady) hipchk(e, "walk window stream");
-                  }
-                  if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > tmo)
-                    throw pe::ExchangeError("host exchange: rank " + std::to_string(r) +
-                                            "'s candidate lists never arrived (peer stalled or failed; PE_HX_TIMEOUT_S)");
-                }
-              }
-              *waited += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-            }
-            const auto tm = trace ? std::chrono::steady_clock::now() : t0;
-            // this share's next groups on their way from DRAM (the device wrote them past the CPU caches;
-            // a line fetched before the device's write is snooped out again, harmless) -- the heads the
-            // merge reads, not whole slots -- and the output lines owned for writing
-            for (int a = 1; a <= 2 && w + a * T < Wg; ++a) {
-              const int wn = w + a * T;
-              for (int r = 0; r < ctx->world; ++r) {
-                const uint8_t* gl = hw->host + (size_t)r * hw->slot + (size_t)wn * gb;
-                for (size_t o = 0; o < pf_bytes; o += 64) __builtin_prefetch(gl + o, 0, 3);
-              }
-              uint8_t* ol = outbuf(b) + (size_t)wn * gb;
-              for (size_t o = 0; o < gb; o += 64) __builtin_prefetch(ol + o, 1, 3);
-            }
-            host_merge_zc(hw->host, hw->slot, w, outbuf(b), gen);
-            if (trace) {
-              *spun += std::chrono::duration<double, std::micro>(tm - ts).count();
-              *merged += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tm).count();
-            }
-          }
-        };
-        struct Times {
-          double waited = 0, spun = 0, merged = 0, busy = 0;   // busy: the share's wall time less its waits
-        };
-        Times tt[kMaxMergers + 1];
-        auto timed_share = [&share](int t, Times* x) {
-          const auto a = std::chrono::steady_clock::now();
-          share(t, &x->waited, &x->spun, &x->merged);
-          x->busy = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count() - x->waited;
-        };
-        for (int t = 1; t < T; ++t) {
-          Times* x = &tt[t];
-          xmergers[(size_t)t - 1]->wait();   // (the warm-up task, before the first window)
-          xmergers[(size_t)t - 1]->post([&timed_share, t, x] { timed_share(t, x); });
-        }
-        std::exception_ptr err;
-        try {
-          timed_share(0, &tt[0]);
-        } catch (...) {
-          err = std::current_exception();
-        }
-        for (int t = 1; t < T; ++t) try {   // every helper is done with the window before it is released
-            xmergers[(size_t)t - 1]->wait();
-          } catch (...) {
-            if (!err) err = std::current_exception();
-          }
-        if (err) std::rethrow_exception(err);
-        double busy = 0, spun = 0, merged = 0;
-        for (int t = 0; t < T; ++t) {
-          busy = std::max(busy, tt[t].busy);   // the merge's critical path: the busiest share (they run side by side)
-          spun += tt[t].spun;
-          merged += tt[t].merged;
-        }
-        if (trace) {
-          tr_xspin.push_back(spun);
-          tr_xmerge.push_back(merged);
-        }
-        const double all_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ctx->stats.xchg_merge_ms += busy;
-        ctx->stats.xchg_wait_ms += std::max(0.0, all_ms - busy);   // the rest of the window's exchange: waiting
-        pe::hx_zc_consumed(hx, *hw);
-        return;
-      }
-      if (own_direct && ctx->Ns > 0) {   // every own group signalled: the lists are in h_own
-        struct Idle {   // busy while the launcher has not launched the walk yet, or the stream runs
-          const SpinWorker* l;
-          hipStream_t s;
-          static bool busy(void* u) {
-            auto* x = static_cast<Idle*>(u);
-            return (x->l && x->l->busy()) || StreamIdle::stream_busy(x->s);
-          }
-        } idle{launcher, s};
-        pe::WindowFeed own;
-        std::vector<pe::GroupCands> own_cands;
-        own.idle = &Idle::busy;
-        own.idle_user = &idle;
-        own.reset(ctx->h_own.p, Wg, K, gen, &own_cands);
-        own.wait((size_t)Wg - 1);
-      } else {
-        hipchk(hipMemcpyAsync(ctx->h_own.p, ctx->g_out.p, bytes, hipMemcpyDeviceToHost, s), "D2H cands");
-        hipchk(hipStreamSynchronize(s), "sync own cands");
-      }
-      const auto tx = std::chrono::steady_clock::now();
-      if (ctx->exchange(ctx->exchange_user, ctx->h_own.p, dev_merge ? ctx->h_xg[b].p : outbuf(b), bytes) != 0)
-        raise(PE_ERCCL, "exchange callback failed");
-      ctx->stats.xchg_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx).count();
-      if (xhost_merge) {
-        const auto tm = std::chrono::steady_clock::now();
-        for (int w = 0; w < Wg; ++w) host_merge_group(ctx->h_xg[b].p, Wg, w, outbuf(b), gen);
-        ctx->stats.xchg_merge_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm).count();
-      } else if (dev_merge) {   // the gathered lists (pinned) merged on the device, signalled per group
-        hipchk(merge_fn(s, ctx->h_xg[b].dev, ctx->world, Wg, K, outbufdev(b), gen, 0, nullptr, true),
-               "launch merge_shards");
-      }
-    };
-    // gen_in: the window's generation assigned by the caller (split exchange: the exchange thread
-    // must know it before the launch); defer_x: leave the exchange to the exchange thread
-    auto enqueue_window = [&](const std::vector<int32_t>& groups, int b, uint32_t gen_in = 0, bool defer_x = false,
-                              const pe::HxWindow* hw_in = nullptr) {
-      const int Wg = (int)groups.size();
-      const int Wgp = (int)round_up(Wg, pe::SC_GT);
-      const int Kw = rccl_grow ? k_win : K;   // the window's list stride (RCCL: its length, see rccl_grow)
-      auto& hg = hgroups(b);
-      for (int w = 0; w < Wgp; ++w) {
-        const int g = groups[std::min(w, Wg - 1)];
-        fill_req(hg.p[w], R.scan_req(g), group_need[g]);   // island groups: count x request
-      }
-      // unsharded: the kernel writes the blob straight into pinned host memory (no D2H copy); so does
-      // a pipelined host exchange's walk (its own lists, signalled per group: no D2H, no stream sync)
-      const bool own_direct = walk && use_exchange && pipelined && !zc;
-      pe::HxWindow hw;   // zero-copy: this window's slots and their generation (every rank, every window)
-      if (zc) {
-        hw = hw_in ? *hw_in : pe::hx_zc_next(hx);
-        if (zc_host && !pe::hx_zc_wait_reuse(hx, hw))   // (every rank read the window that used the slots)
-          throw pe::ExchangeError("host exchange: a rank never finished reading a window (peer stalled or failed)");
-      }
-      uint8_t* const dst = zc           ? hw.dev + (size_t)ctx->rank * hw.slot
-                           : direct_out ? outbufdev(b)
-                           : own_direct ? ctx->h_own.dev
-                                        : ctx->g_out.p;
-      uint32_t gen = 0;   // signalled window: its generation (the walk's or the shard merge's)
-      if (gen_in) {
-        gen = gen_in;
-      } else if (signalled || own_direct) {
-        if (++ctx->walk_gen == 0) ++ctx->walk_gen;
-        gen = ctx->walk_gen;
-      }
-      buf_gen[b] = gen;
-      buf_k[b] = Kw;
-      if (walk) {   // one 64-B request per block: read from pinned host memory, no H2D copy
-        // PE_WALK_SWITCH_DELAY=n (test knob): take a finished rebuild over only after n windows ran
-        // with it pending, so the dual overlay writes of those windows' applies are exercised
-        if (ctx->w_pending && (ctx->w_est > ctx->resort_nodes + kResortLate ||
-                               (ctx->w_pend_windows++ >= switch_delay && hipEventQuery(ctx->w_ev_done) == hipSuccess)))
-          walk_switch(ctx);
-        if (!ctx->w_pending) {
-          if (async_resort && ctx->w_est > ctx->resort_nodes - kResortEarly) walk_resort_async(ctx);
-          else if (ctx->w_est > ctx->resort_nodes) walk_resort(ctx);
-        }
-        std::pair<hipEvent_t, hipEvent_t> evp{nullptr, nullptr};
-        if (wflush) hipchk(hipMemsetD32Async((hipDeviceptr_t)ctx->w_flush.p, ctx->walk_gen, (size_t)128 << 20, s), "flush");
-        if (wev) {
-          hipchk(hipEventCreate(&evp.first), "event");
-          hipchk(hipEventCreate(&evp.second), "event");
-          walk_events.push_back(evp);
-          hipchk(hipEventRecord(evp.first, s), "event record");
-        }
-        hipchk(pe::launch_walk(s, hg.dev, Wg, k_win, walk_index(ctx), ctx->res.p, ctx->stride, ctx->labels.p, ctx->Ns,
-                               (uint64_t)ctx->begin, dst, zc ? hw.gen : direct_out || own_direct ? gen : 0u, Kw),
-               "launch walk");
-        if (wev) hipchk(hipEventRecord(evp.second, s), "event record");
-        walk_launch_groups += Wg;
-      } else if (ctx->Ns > 0) {
-        hipchk(hipMemcpyAsync(ctx->g_groups.p, hg.p, Wgp * sizeof(ReqRec), hipMemcpyHostToDevice, s), "H2D window");
-        hipchk(pe::launch_scan(s, ctx->res.p, ctx->stride, ctx->labels.p, ctx->g_kn.p, ctx->g_lo.p, ctx->Ns,
-                               (uint64_t)ctx->begin, ctx->g_groups.p, Wg, ctx->g_cand.p, ctx->g_cnt.p, ctx->g_bound.p,
-                               nwaves),
-               "launch scan");
-        hipchk(pe::launch_merge(s, ctx->g_cand.p, ctx->g_cnt.p, ctx->g_bound.p, nwaves, K, dst, Wg),
-               "launch merge");
-      } else if (zc) {   // an empty shard: empty lists, signalled in stream order like a walk's
-        hipchk(pe::launch_empty_groups(s, Wg, Kw, dst, hw.gen), "launch empty groups");
-      } else {
-        const size_t gbw = pe::cand_group_bytes(Kw);
-        std::vector<uint8_t> empty((size_t)Wg * gbw, 0);
-        for (int w = 0; w < Wg; ++w) {
-          pe::CandHdr h{0, 0, pe::NO_KEY};
-          std::memcpy(empty.data() + (size_t)w * gbw, &h, sizeof(h));
-        }
-        if (direct_out) {
-          std::memcpy(outbuf(b), empty.data(), empty.size());
-        } else {
-          hipchk(hipMemcpyAsync(dst, empty.data(), empty.size(), hipMemcpyHostToDevice, s), "H2D empty");
-          hipchk(hipStreamSynchronize(s), "sync empty");
-        }
-      }
-      const size_t bytes = (size_t)Wg * pe::cand_group_bytes(Kw);
-      if (direct_out) {
-        // written in place
-      } else if (zc_host) {   // the exchange thread (or, not deferred, this thread) merges on the host
-        ctx->stats.xchg_zc_windows += 1;
-        if (!defer_x) exchange_window(b, Wg, gen, false, nullptr, &hw);
-      } else if (zc) {   // merged once every rank's walk signalled every group (pe_hostx.h)
-        ctx->stats.xchg_zc_windows += 1;
-        hipchk(pe::launch_xwait(s, hw.dev, ctx->world, Wg, K, (int64_t)hw.slot, hw.gen, zc_ticks, ctx->g_xstatus.p),
-               "launch exchange wait");
-        hipchk(merge_fn(s, hw.dev, ctx->world, Wg, K, outbufdev(b), gen, (int64_t)hw.slot,
-                                       ctx->g_xstatus.p, true),
-               "launch merge_shards");
-      } else if (use_exchange) {
-        if (!pipelined)
-          hipchk(hipMemcpyAsync(ctx->h_own.p, ctx->g_out.p, bytes, hipMemcpyDeviceToHost, s), "D2H cands");
-        else if (!defer_x)   // (the launch helper, or the main thread at a restart) exchange now
-          exchange_window(b, Wg, gen, own_direct, nullptr);
-      } else {
-        if (stall_window >= 0 && ctx->stats.windows == stall_window && stall_ticks > 0)
-          hipchk(pe::launch_stall(s, stall_ticks), "launch stall (test knob)");
-        ncclchk(ncclAllGather(ctx->g_out.p, ctx->g_gath.p, bytes, ncclUint8, ctx->comm, s), "ncclAllGather");
-        if (dev_merge)
-          hipchk(merge_fn(s, ctx->g_gath.p, ctx->world, Wg, Kw, outbufdev(b), gen, 0, nullptr, false),   // (device lists)
-                 "launch merge_shards");
-        else
-          hipchk(hipMemcpyAsync(outbuf(b), ctx->g_gath.p, bytes * ctx->world, hipMemcpyDeviceToHost, s),
-                 "D2H gathered");
-      }
-      ctx->stats.windows += 1;
-      ctx->stats.groups_scanned += Wg;
-      if (!walk) ctx->stats.scan_evals += (int64_t)Wg * ctx->Ns;
-    };
-    // ---- wait for the window's blob (and run the host exchange when one is configured), parse it
-    auto collect_window = [&](const std::vector<int32_t>& groups, int b) {
-      const int Wg = (int)groups.size();
-      const size_t bytes = (size_t)Wg * gb;
-      const auto tw = std::chrono::steady_clock::now();
-      if (signalled && buf_gen[b] != 0) {   // the first group's list (and so every earlier launch) is done
-        last_blob = outbuf(b);
-        feed.reset(outbuf(b), Wg, buf_k[b], buf_gen[b], &cands);
-        feed.wait(0);
-        feed_spin_seen = feed.spin_ms();
-        const auto th = std::chrono::steady_clock::now();
-        ctx->stats.greedy_wait_ms += std::chrono::duration<double, std::milli>(th - tw).count();
-        if (trace) tr_wait.push_back(std::chrono::duration<double, std::micro>(th - tw).count());
-        return;
-      }
-      sync_stream("sync window");
-      last_blob = outbuf(b);
-      if (use_exchange && !pipelined) {
-        const auto tx = std::chrono::steady_clock::now();
-        if (ctx->exchange(ctx->exchange_user, ctx->h_own.p, outbuf(b), bytes) != 0)
-          raise(PE_ERCCL, "exchange callback failed");
-        ctx->stats.xchg_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx).count();
-        if (dev_merge) {   // the gathered blob (pinned) merged by the device into h_merged
-          hipchk(merge_fn(s, outbufdev(b), ctx->world, Wg, K, ctx->h_merged.dev, 0u, 0, nullptr, true),
-                 "launch merge_shards");
-          sync_stream("sync merge");
-          last_blob = ctx->h_merged.p;
-        }
-      }
-      const auto th = std::chrono::steady_clock::now();
-      ctx->stats.greedy_wait_ms += std::chrono::duration<double, std::milli>(th - tw).count();
-      if (trace) tr_wait.push_back(std::chrono::duration<double, std::micro>(th - tw).count());
-      pe::parse_window_keys(last_blob, dev_merge ? 1 : ctx->world, Wg, buf_k[b], cands);   // lists point into the blob
-
-      ctx->stats.greedy_host_ms +=
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th).count();
-    };
-    // ---- residual updates of this shard: the apply kernel reads the records from pinned staging
-    //      slot `slot` (no H2D copy); a slot is rewritten only once a later launch is known to have
-    //      started (a signalled group seen, or a stream sync) -- the pipelined loop below rotates D
-    auto enqueue_apply = [&](const std::vector<pe::Update>& updates, int slot) {
-      int64_t nu = 0;
-      HostBuf<int64_t>& hu = slot == 0 ? ctx->h_upd : ctx->h_updx[slot - 1];
-      hipchk(hu.ensure(std::max<size_t>(updates.size(), 1) * (pe::D + 1), kZeroCopy), "alloc pinned upd");
-      for (const pe::Update& u : updates) {
-        if (u.gid < ctx->begin || u.gid >= ctx->end) continue;
-        int64_t* o = hu.p + nu * (pe::D + 1);
-        o[0] = u.gid - ctx->begin;
-        for (int d = 0; d < pe::D; ++d) o[1 + d] = u.res[d];
-        ++nu;
-      }
-      if (nu > 0) {   // the kernel reads the pinned records directly (no H2D copy)
-        const pe::WalkIndex w = walk_index(ctx);
-        const pe::WalkIndex wn = walk_index(ctx, 1 - ctx->w_cur);   // (read only while a rebuild is pending)
-        hipchk(pe::launch_apply(s, ctx->res.p, ctx->stride, hu.dev, nu, (uint64_t)ctx->begin, ctx->g_kn.p,
-                                ctx->g_lo.p, ctx->labels.p, walk ? &w : nullptr,
-                                walk && ctx->w_pending ? &wn : nullptr),
-               "launch apply");
-        ctx->w_est += nu;
-        if (ctx->w_pending) {
-          ctx->w_pend_est += nu;
-          ctx->stats.walk_pend_updates += nu;   // applied into both index sets' overlays
-        }
-      }
-    };
-    auto timed_resolve = [&](const std::vector<int32_t>& groups, std::vector<pe::Update>& updates,
-                             const std::vector<pe::Update>* seed) {
-      if (dump && dump_left-- == 0) {   // PE_DUMP_MAX_WINDOWS reached
-        std::fclose(dump);
-        dump = nullptr;
-      }
-      if (dump) {   // {Wg, groups, blob, n_seed, seeds}: what this resolve call reads
-        if (signalled) feed.wait(groups.size() - 1);   // (diagnostics: the whole blob first)
-        const int32_t wg = (int32_t)groups.size(), ns = seed ? (int32_t)seed->size() : 0;
-        std::fwrite(&wg, 4, 1, dump);
-        std::fwrite(groups.data(), 4, (size_t)wg, dump);
-        std::fwrite(last_blob, 1, (size_t)wg * gb * (dev_merge || direct_out ? 1 : ctx->world), dump);
-        std::fwrite(&ns, 4, 1, dump);
-        if (ns) std::fwrite(seed->data(), sizeof(pe::Update), (size_t)ns, dump);
-      }
-      const auto th = std::chrono::steady_clock::now();
-      updates.clear();
-      const bool fed = signalled && buf_gen[cb] != 0;
-      const bool consumed = R.resolve(groups, cands, updates, seed, fed ? &feed : nullptr);
-      // time the resolver spent blocked on groups not yet signalled is device wait, not host work
-      const double spun = fed ? feed.spin_ms() - feed_spin_seen : 0.0;
-      if (trace) tr_res.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th).count() -
-                                  spun * 1e3);
-      for (const pe::Update& u : updates)          // the mirror follows every placement (all shards)
-        for (int d = 0; d < pe::D; ++d) ctx->m_nodes[u.gid].res[d] = u.res[d];
-      ctx->stats.greedy_host_ms +=
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th).count() - spun;
-      ctx->stats.greedy_wait_ms += spun;
-      return consumed;
-    };
-
-    // Pipelined (exact), depth D: while the host resolves window i, the device holds windows
-    // i+1 .. i+D scanned (or scanning), each speculating that the windows before it are consumed.  A
-    // window scanned after the updates of the epoch's windows < v were applied misses the changes of
-    // windows v .. i-1, which its resolution takes as dirty seeds (their current states are known
-    // here).  Each iteration the helper thread applies the previous window's updates and scans the
-    // window D ahead into the next free buffer.  A window cut short, or a cursor that did not land
-    // where the speculation started, syncs, applies everything and restarts from the cursor.
-    // Staging-buffer reuse: the apply posted in iteration j is followed, in the same post, by the
-    // scan of window j + D; the slot is written again in iteration j + D, when that window's first
-    // group has been seen, i.e. after every earlier launch of the stream finished (with the early post
-    // below, two slots: see early_post).  Blob / request buffer b is reused D + 1 windows later, after
-    // the windows in between were resolved.
-    struct Flight {
-      std::vector<int32_t> groups;
-      pe::Cursor end;
-      int buf = 0;
-      size_t ver = 0;   // updates of the epoch's windows [0, ver) were applied before its scan
-    };
-    std::deque<Flight> fl;
-    std::vector<std::vector<pe::Update>> hist;   // updates of the epoch's resolved windows
-    size_t n_app = 0;                             // of which posted for apply
-    int next_buf = 0, upd_slot = 0;
-    // Early post (signalled windows at depth 1, one rank or a non-split exchange; PE_EARLY_POST=0: off,
-    // A/B; unsignalled windows share one request buffer, which the next walk may still read): once window i
-    // landed, the helper is given apply(i) and the scan of window i + 2 at once -- queued behind the walk
-    // of window i + 1 -- instead of after the first group of window i + 1 was seen, so the device never
-    // idles while the host posts them.  The apply records then need two staging slots: apply(i) may be
-    // written while apply(i - 1) has not run yet; the slot it reuses was read by apply(i - 2), which ran
-    // before the walk of window i, all of whose groups were resolved.
-    const bool early_post = signalled && depth == 1 && !split_x &&
-                            !(std::getenv("PE_EARLY_POST") && std::atoi(std::getenv("PE_EARLY_POST")) == 0);
-    const int upd_slots = early_post ? 2 : std::max(depth, 1);
-    bool posted = false;   // the helper already has this iteration's task (early post)
-    const int nbuf = std::max(depth, 1) + 1;
-    auto add_flight = [&](const pe::Cursor& from) -> Flight* {   // main thread; nullptr: no window left
-      Flight f;
-      R.next_window_from(from, Wmax, ctx->window_pods, f.groups, &f.end);
-      if (f.groups.empty()) return nullptr;
-      f.buf = next_buf;
-      next_buf = (next_buf + 1) % nbuf;
-      f.ver = hist.size();
-      fl.push_back(std::move(f));
-      return &fl.back();
-    };
-    auto restart = [&]() {   // nothing in flight, every update applied: a fresh epoch at the cursor
-      fl.clear();
-      hist.clear();
-      n_app = 0;
-      next_buf = 0;
-      Flight* f = add_flight(R.cursor());
-      if (!f) return;
-      if (split_x && zc_host) {
-        // a zero-copy window: merged group by group on the exchange thread as in the loop below, so
-        // the resolver starts on the first merged group (merging the whole window here first put the
-        // walk's tail and the full merge in front of every batch start and every rescan)
-        if (++ctx->walk_gen == 0) ++ctx->walk_gen;
-        const uint32_t gen = ctx->walk_gen;
-        const pe::HxWindow hw = pe::hx_zc_next(hx);
-        enqueue_window(f->groups, f->buf, gen, true, &hw);
-        const int b = f->buf, wg = (int)f->groups.size();
-        xworker->post([&, b, wg, gen, hw] { exchange_window(b, wg, gen, true, worker.get(), &hw); });
-      } else {
-        enqueue_window(f->groups, f->buf);
-      }
-    };
-    const auto t_setup = std::chrono::steady_clock::now();
-    restart();
-    std::vector<pe::Update> seed, upd;
-    while (!fl.empty()) {
-      Flight& cur = fl.front();
-      cb = cur.buf;
-      collect_window(cur.groups, cur.buf);       // cur's lists: snapshot = device state at its launch
-      if (!pipelined) {
-        if (!timed_resolve(cur.groups, upd, nullptr)) k_win = K;
-        enqueue_apply(upd, 0);
-        if (R.done()) break;
-        fl.clear();
-        next_buf = 0;
-        if (Flight* f = add_flight(R.cursor())) enqueue_window(f->groups, f->buf);
-        continue;
-      }
-      // the helper: previous windows' updates applied, then windows scanned up to D ahead
-      std::vector<std::pair<const std::vector<pe::Update>*, int>> to_apply;
-      std::vector<Flight*> to_scan;
-      auto plan_post = [&]() {
-        to_apply.clear();
-        to_scan.clear();
-        for (; n_app < hist.size(); ++n_app) {
-          to_apply.emplace_back(&hist[n_app], upd_slot);
-          upd_slot = (upd_slot + 1) % upd_slots;
-        }
-        while ((int)fl.size() < depth + 1)
-          if (Flight* f = add_flight(fl.back().end)) to_scan.push_back(f);
-          else break;
-      };
-      auto post_scan = [&]() {   // (the non-split helper task)
-        worker->post([&, to_apply, to_scan] {
-          const auto tp = std::chrono::steady_clock::now();
-          if (trace) helper_cpu = sched_getcpu();
-          for (const auto& a : to_apply) enqueue_apply(*a.first, a.second);
-          for (Flight* f : to_scan) enqueue_window(f->groups, f->buf);
-          if (trace) tr_post.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp).count());
-        });
-      };
-      if (posted) {
-        posted = false;
-      } else if (split_x) {
-        plan_post();
-        // generations assigned here, in launch order: the exchange thread waits for these windows' own
-        // lists (signalled with them) while the launch helper launches the walks
-        // (zero-copy: the windows' slots too, taken in the same order on every rank)
-        struct XWin {
-          int buf, wg;
-          uint32_t gen;
-          pe::HxWindow hw;
-        };
-        std::vector<XWin> xs;
-        std::vector<std::pair<Flight*, XWin>> ws;
-        for (Flight* f : to_scan) {
-          if (++ctx->walk_gen == 0) ++ctx->walk_gen;
-          xs.push_back(XWin{f->buf, (int)f->groups.size(), ctx->walk_gen, zc_host ? pe::hx_zc_next(hx) : pe::HxWindow{}});
-          ws.emplace_back(f, xs.back());
-        }
-        const auto txb = std::chrono::steady_clock::now();
-        // (the copying exchange: the previous window's exchange is over before the next one, its
-        // buffers are shared; host-merged zero-copy windows queue up -- slot reuse is counted)
-        if (!zc_host) xworker->wait();
-        if (trace) tr_xblock.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - txb).count());
-        worker->post([&, to_apply, ws] {
-          const auto tp = std::chrono::steady_clock::now();
-          if (trace) helper_cpu = sched_getcpu();
-          for (const auto& a : to_apply) enqueue_apply(*a.first, a.second);
-          for (const auto& w : ws)
-            enqueue_window(w.first->groups, w.first->buf, w.second.gen, true, zc_host ? &w.second.hw : nullptr);
-          if (trace) tr_post.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp).count());
-        });
-        xworker->post([&, xs] {
-          for (const XWin& x : xs) exchange_window(x.buf, x.wg, x.gen, true, worker.get(), zc_host ? &x.hw : nullptr);
-        });
-      } else {
-        plan_post();
-        post_scan();
-      }
-      // seeds: the changes of the windows resolved since cur's scan (later states overwrite)
-      seed.clear();
-      for (size_t k = cur.ver; k < hist.size(); ++k) seed.insert(seed.end(), hist[k].begin(), hist[k].end());
-      bool consumed = false;
-      try {
-        consumed = timed_resolve(cur.groups, upd, &seed);
-      } catch (...) {
-        // the helper task still reads the flights and update sets: let it finish before the
-        // unwinding frees them, then report the resolver's error (the helper's is secondary)
-        try {
-          worker->wait();
-        } catch (...) {
-        }
-        if (xworker) xworker->wait();   // (a failed exchange is the cause: its error wins)
-        throw;
-      }
-      worker->wait();
-      const bool landed = consumed && R.cursor() == cur.end && fl.size() > 1;
-      if (landed && !R.done()) {
-        hist.push_back(std::move(upd));
-        upd = {};
-        fl.pop_front();
-        if (early_post) {   // the next iteration's task, now
-          plan_post();
-          post_scan();
-          posted = true;
-        }
-        continue;
-      }
-      // done, or speculation dropped: finish the device work, apply what is left, in order (one
-      // launch per window: a node may be in several windows' updates)
-      if (xworker) xworker->wait();   // (its merge launch first: it is stream work too)
-      sync_stream("sync speculative");
-      for (; n_app < hist.size(); ++n_app) {   // (depth > 1 only; slot 0 is rewritten after each)
-        enqueue_apply(hist[n_app], 0);
-        sync_stream("sync apply");
-      }
-      enqueue_apply(upd, 0);
-      if (R.done()) break;
-      if (!consumed) k_win = K;   // lists ran out: longer ones from here (the helper is idle now)
-      restart();
-    }
-    const auto t_loop = std::chrono::steady_clock::now();
-    if (xworker) xworker->wait();
-    sync_stream("sync greedy");
-    walk_drop_pending(ctx);   // (the next call rebuilds in line anyway)
-    if (walk) {
-      unsigned long long wc[2] = {0, 0};
-      hipchk(hipMemcpy(wc, ctx->w_stat.p, sizeof(wc), hipMemcpyDeviceToHost), "D2H walk counters");
-      ctx->stats.walk_rounds += (int64_t)wc[0];
-      ctx->stats.walk_overlay += (int64_t)wc[1];
-      ctx->stats.walk_groups += walk_launch_groups;
-      ctx->stats.walk_prepass += walk_launch_groups * ((ctx->Ns + pe::WK_ROUND - 1) / pe::WK_ROUND);
-      for (auto& p : walk_events) {
-        float ms = 0.f;
-        hipchk(hipEventElapsedTime(&ms, p.first, p.second), "event elapsed");
-        ctx->stats.walk_ms += ms;
-      }
-    }
-    if (P > 0) std::memcpy(out_pod_node, R.pod_node().data(), (size_t)P * 4);
-    std::memcpy(out_job_status, R.job_status().data(), (size_t)n_jobs * 4);
-    ctx->stats.rescans += R.rescans();
-    ctx->stats.pods_placed += R.pods_placed();
-    ctx->stats.jobs_placed += R.jobs_placed();
-    ctx->stats.jobs_failed += R.jobs_failed();
-    ctx->stats.last_greedy_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (trace) {
-      auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::micro>(b - a).count();
-      };
-      std::fprintf(stderr, "greedy phases (us): checks+prep %.0f resolver %.0f setup %.0f loop %.0f tail %.0f\n",
-                   us(t0, t_prep), us(t_prep, t_res), us(t_res, t_setup), us(t_setup, t_loop),
-                   us(t_loop, std::chrono::steady_clock::now()));
-    }
-    return PE_OK;
-  });
-}
 
 int pe_fit_mask_layout(const pe_ctx* ctx, int32_t* layout) {
   if (!ctx || !layout) return PE_EINVAL;

@@ -8,7 +8,7 @@
 // device for every rank's signal of its group before merging.  No host thread, no barrier, no
 // copy: a group's merged list is signalled as soon as the last rank's walk wrote it.
 //
-// Two ways to merge (pe_engine.cpp): by default each rank's exchange thread polls the slot headers
+// Two ways to merge (pe_engine_greedy.cpp): by default each rank's exchange thread polls the slot headers
 // in host memory and merges group by group on the host, as soon as every rank's walk wrote the
 // group (no kernel, no PCIe read-back); slot reuse then waits for every rank's consumed count.
 // PE_ZC_DEV_MERGE=1: a one-block device wait plus the shard merge kernel queued behind the walk;
@@ -41,7 +41,7 @@ bool hx_zc_register(pe_host_exchange* x);
 size_t hx_slot_bytes(const pe_host_exchange* x);
 // the next zero-copy window (every rank calls it once per window, in the same order)
 HxWindow hx_zc_next(pe_host_exchange* x);
-// Host-merged windows (the default, pe_engine.cpp): every rank's exchange thread reads all slots of
+// Host-merged windows (the default, pe_engine_greedy.cpp): every rank's exchange thread reads all slots of
 // a window, so a slot is rewritten (window index + 2, same phase) only after every rank said it
 // read window index: hx_zc_consumed after the last group, hx_zc_wait_reuse before the walk that
 // rewrites it (false: PE_HX_TIMEOUT_S passed).

@@ -1,4 +1,4 @@
-// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp launches
+// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp and pe_engine_greedy.cpp launches
 // these through the wrappers below; nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

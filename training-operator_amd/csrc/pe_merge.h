@@ -1,4 +1,4 @@
-// Host merge of per-rank candidate lists (the zero-copy shared-memory exchange, pe_engine.cpp): the
+// Host merge of per-rank candidate lists (the zero-copy shared-memory exchange, pe_engine_greedy.cpp): the
 // rule of merge_shards_kernel on the host -- the keys below the smallest rank limit L, the Kc + 1
 // smallest of them; the merged list holds the first Kc, its limit is the (Kc+1)-th key, else L.
 // Pure host code (no HIP), so tools/bench_merge.cc times exactly what the exchange thread runs.
