@@ -62,6 +62,8 @@ const (
 	CapMax = int32(C.PE_CAP_MAX)
 	// MaxDomains bounds GangCapacityDomains' nDomains.
 	MaxDomains = int32(C.PE_MAX_DOMAINS)
+	// MaxLevels bounds GangCapacityTree's levels.
+	MaxLevels = int32(C.PE_MAX_LEVELS)
 )
 
 // Node inventory update ops.
@@ -647,6 +649,62 @@ func (e *Engine) GangCapacityDomains(req []int64, need []uint32, count []int32, 
 	rc := C.pe_gang_capacity_domains(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(count), C.int32_t(nDomains),
 		ptr64(out.DomSlots), ptr64(out.DomNodes), ptr32(out.Domain), ptr64(out.DomainSlots), ptr32(out.Feasible))
 	return out, e.err(rc, "pe_gang_capacity_domains")
+}
+
+// TreeCapacity is GangCapacityTree's answer; a part that was not asked for is nil.  T is the sum of the
+// level sizes; the column of domain k of level l is the sum of the lower levels' sizes plus k.
+type TreeCapacity struct {
+	TreeSlots   []int64 // [J][T]: pods of job j's shape that each domain of each level holds
+	TreeNodes   []int64 // [J][T]: its nodes holding at least one
+	Level       []int32 // [J]: the lowest level <= maxLevel at which one domain holds the gang; -1 = none
+	Domain      []int32 // [J]: that level's domain with the smallest slots >= count, ties to the smallest id; -1 = none
+	DomainSlots []int64 // [J]: that domain's slots, 0 when none
+	Feasible    []int32 // [J][nLevels]: domains of each level with slots >= count
+}
+
+// GangCapacityTree answers GangCapacityDomains' question over a hierarchy of topology levels (node -> rack
+// -> block -> zone): levelSize[l] domains at level l, level 0 being the nodes' island ids, and
+// parent[off_l+k] the level-(l+1) domain that holds domain k of level l, or -1 (nil allowed with one
+// level).  tables asks for the [J][T] tables.  With count ([J], each >= 1) the device also picks, per
+// job, the lowest level <= maxLevel[j] (nil: the top level) at which one domain holds the gang, and the
+// best-fitting domain there; with tables false only those answers cross.  count nil: no selection.  A
+// sharded engine answers tables only: add the shards' tables, then select.  Read-only, like GangCapacity.
+func (e *Engine) GangCapacityTree(req []int64, need []uint32, count, maxLevel, levelSize, parent []int32, tables bool) (*TreeCapacity, error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, fmt.Errorf("GangCapacityTree: %d needs for %d jobs", len(need), J)
+	}
+	if count != nil && len(count) != J {
+		return nil, fmt.Errorf("GangCapacityTree: %d counts for %d jobs", len(count), J)
+	}
+	if maxLevel != nil && (count == nil || len(maxLevel) != J) {
+		return nil, fmt.Errorf("GangCapacityTree: %d max levels for %d jobs with a count", len(maxLevel), J)
+	}
+	L := len(levelSize)
+	valid := L >= 1 && L <= int(MaxLevels)
+	T := 0
+	for _, s := range levelSize {
+		valid = valid && s >= 1 && s <= MaxDomains
+		T += int(s)
+	}
+	if valid && parent != nil && len(parent) != T-int(levelSize[L-1]) {
+		return nil, fmt.Errorf("GangCapacityTree: %d parents for %d columns below the top level", len(parent), T-int(levelSize[L-1]))
+	}
+	out := &TreeCapacity{}
+	if tables && valid {
+		out.TreeSlots = make([]int64, J*T)
+		out.TreeNodes = make([]int64, J*T)
+	}
+	if count != nil && valid {
+		out.Level = make([]int32, J)
+		out.Domain = make([]int32, J)
+		out.DomainSlots = make([]int64, J)
+		out.Feasible = make([]int32, J*L)
+	}
+	rc := C.pe_gang_capacity_tree(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(count), ptr32(maxLevel),
+		C.int32_t(L), ptr32(levelSize), ptr32(parent), ptr64(out.TreeSlots), ptr64(out.TreeNodes), ptr32(out.Level),
+		ptr32(out.Domain), ptr64(out.DomainSlots), ptr32(out.Feasible))
+	return out, e.err(rc, "pe_gang_capacity_tree")
 }
 
 // Gangs is a greedy placement batch: jobs of groups of identical pods (include/placement.h).

@@ -378,6 +378,56 @@ int pe_gang_capacity_domains(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[
                              int64_t* out_dom_nodes /*[j][n_domains] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
                              int64_t* out_domain_slots /*[j] or NULL*/, int32_t* out_feasible /*[j] or NULL*/);
 
+/* (ABI 7, additive) Gang capacity over a topology hierarchy, such as node -> rack -> block -> zone: what is
+ * the LOWEST level at which one domain holds the whole gang, and which domain of that level fits it best --
+ * the question of topology-aware gang admission (Kueue's topology-aware scheduling: a gang that fits no
+ * rack may fit one block; one with a "required: rack" policy must not be admitted at block level).
+ * Levels and columns: level 0 is the leaf level, whose domains are the island ids in [0, level_size[0])
+ * exactly as in pe_gang_capacity_domains (a node with another id, and a removed slot, counts nowhere at
+ * any level).  n_levels in [1, PE_MAX_LEVELS], every level_size[l] in [1, PE_MAX_DOMAINS], T = the sum of
+ * the level sizes.  The column of domain k of level l is off_l + k, off_0 = 0, off_{l+1} = off_l + level_size[l].
+ * Parent map, an argument of the call (nothing about it is kept in the context): parent[off_l + k] is the
+ * level-(l + 1) domain that contains domain k of level l, in [0, level_size[l + 1]), or -1: the domain
+ * counts at its own level and nowhere above.  The top level has no entries.
+ * Tables, against the CURRENT residuals of this shard:
+ *   out_tree_slots[j][off_0 + k], out_tree_nodes[j][off_0 + k] = pe_gang_capacity_domains' out_dom_slots[j][k],
+ *                                    out_dom_nodes[j][k] for n_domains = level_size[0]
+ *   out_tree_slots[j][off_{l+1} + p] = sum of out_tree_slots[j][off_l + c] over the children c with
+ *                                    parent[off_l + c] == p; out_tree_nodes by the same rule
+ * Every node counts at most once per level, so all sums stay below 2^55: exact int64.
+ * Selection, on the device (requested by any non-NULL out_level, out_domain, out_domain_slots or
+ * out_feasible; the tables may be NULL and then never cross):
+ *   out_level[j]        = the smallest l <= max_level[j] at which some domain has out_tree_slots >= count[j];
+ *                         -1 if there is none.  "Required at level r" is max_level[j] = r; "preferred
+ *                         lowest" is max_level NULL (= n_levels - 1 for every job).
+ *   out_domain[j]       = the domain of that level (its id within the level, not its column) with the
+ *                         smallest such slots, ties to the smallest id; -1 when none
+ *   out_domain_slots[j] = that domain's slots, 0 when none
+ *   out_feasible[j][l]  = number of level-l domains with out_tree_slots >= count[j], for EVERY level,
+ *                         those above max_level[j] included
+ * A selection requires count with every count[j] >= 1 and every max_level[j] in [0, n_levels); without one
+ * neither array is read.  With n_levels == 1 every output equals the corresponding output of
+ * pe_gang_capacity_domains (out_level 0 or -1).
+ * Sharded contexts, as pe_gang_capacity_domains: the tables are per shard and the caller adds them over
+ * the shards (the roll-up is linear, so the summed table is the global one); with world_size > 1 a
+ * non-NULL selection output is PE_EINVAL.
+ * Read-only: residuals, the staged fit-mask state and everything a later pe_gang_capacity_domains call
+ * relies on are left as they are.  Each out_* may be NULL; need NULL = 0.
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): a negative
+ * request, a count below 1, a max_level out of range, n_levels or a level size out of range, a parent
+ * outside [-1, level_size[l + 1]), a NULL level_size, a NULL parent with n_levels > 1.  PE_ESTATE: a call
+ * before pe_load_nodes.  An empty shard or n_jobs == 0 is PE_OK: tables 0, out_level and out_domain -1,
+ * out_domain_slots and out_feasible 0. */
+#define PE_MAX_LEVELS 4
+int pe_gang_capacity_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/,
+                          const uint32_t* need /* or NULL = 0 */, const int32_t* count /*[j] or NULL*/,
+                          const int32_t* max_level /*[j] or NULL = n_levels - 1*/,
+                          int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                          const int32_t* parent /*[T - level_size[n_levels-1]], NULL allowed when n_levels == 1*/,
+                          int64_t* out_tree_slots /*[j][T] or NULL*/, int64_t* out_tree_nodes /*[j][T] or NULL*/,
+                          int32_t* out_level /*[j] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
+                          int64_t* out_domain_slots /*[j] or NULL*/, int32_t* out_feasible /*[j][n_levels] or NULL*/);
+
 /* Greedy best-fit all-or-nothing gang placement.  Jobs in (priority
  * desc, index asc) order, groups of a job in the given order, pods of a group identical.
  *   job_group_off[J+1], priority[J], group_count[G] (pods to place), group_req[G][4],

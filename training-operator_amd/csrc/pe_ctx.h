@@ -386,6 +386,17 @@ struct pe_ctx {
   HostBuf<pe::DomSel> dm_hsel;
   std::vector<pe::DomPick> dm_upicks;
   std::vector<int32_t> dm_ptab, dm_pof;
+  // gang capacity over a hierarchy (pe_gang_capacity_tree; shapes, dedupe and events are cp_*, the leaf table
+  // and the pinned table copies are dm_table / dm_hslots / dm_hnodes, the pick dedupe is dm_ptab / dm_pof --
+  // every call of either entry point sizes and fills what it uses, so the calls may alternate): the upper
+  // levels' table of one chunk of shapes, the call's roll-up plan, its distinct (shape, count, max_level)
+  // picks and their answers.  Grow and are reused; nothing outlives a call.
+  DevBuf<uint64_t> tr_upper;   // per launch of sc shapes: slots u64 [sc][U], then nodes u32 [sc][U]
+  HostBuf<int32_t> tr_hin;     // one copy in: the plan's words, then (16-B aligned) the P picks
+  DevBuf<int32_t> tr_in;
+  DevBuf<uint32_t> tr_out;     // one copy out: P TreeSel records, then the counts [P][n_levels]
+  HostBuf<uint32_t> tr_hout;
+  std::vector<pe::TreePick> tr_upicks;
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -459,6 +470,7 @@ struct pe_ctx {
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
     dm_table.release(); dm_hslots.release(); dm_hnodes.release(); dm_hpicks.release();
     dm_picks.release(); dm_sel.release(); dm_hsel.release();
+    tr_upper.release(); tr_hin.release(); tr_in.release(); tr_out.release(); tr_hout.release();
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();

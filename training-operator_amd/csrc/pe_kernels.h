@@ -488,4 +488,41 @@ hipError_t launch_gang_capacity_domains(hipStream_t s, const int64_t* res, int64
 hipError_t launch_domain_select(hipStream_t s, const uint64_t* dom_slots, int64_t s0, int64_t S, int n_domains,
                                 const DomPick* picks, int64_t P, DomSel* out);
 
+// ---- gang capacity over a topology hierarchy (pe_gang_capacity_tree, pe_tree.hip; the plan: pe_tree_plan.h)
+constexpr int TR_MAX_LEVELS = 4;                 // PE_MAX_LEVELS
+// A distinct (shape, count, max_level) of a call that asks for a selection; its answer.
+struct TreePick {
+  uint32_t shape;     // index into the call's distinct shapes
+  int32_t count;      // >= 1
+  int32_t max_level;  // in [0, n_levels)
+  int32_t pad_;
+};
+struct TreeSel {
+  uint64_t slots;   // the chosen domain's slots, 0 when none
+  int32_t domain;   // of the lowest level <= max_level that holds the gang: smallest slots >= count, ties to the
+                    // smallest id; -1 when none
+  int32_t level;    // that level, -1 when none
+};
+static_assert(sizeof(TreePick) == 16 && sizeof(TreeSel) == 16, "TreePick / TreeSel layout");
+// The levels of a call, by value: level l has size[l] domains; level 0's rows are the leaf table's, level
+// l >= 1 begins at column col[l] of the upper table's rows (pitch = the sum of the upper sizes).
+struct TreeLevels {
+  int32_t n_levels;
+  int32_t size[TR_MAX_LEVELS];
+  int32_t col[TR_MAX_LEVELS];
+  int32_t pitch;
+};
+// One level from the level below, for S shapes: up[s][p] = sum of lo[s][c] over the children c of parent p
+// (start[n_parents + 1] / child: the level's CSR), slots and -- unless lo_nodes is NULL -- nodes.  lo_* / up_*
+// point at the level's first column; every (s, p) is stored, a childless parent as 0.  width: lanes per
+// parent, a power of two in [1, 64].
+hipError_t launch_tree_rollup(hipStream_t s, const uint64_t* lo_slots, const uint32_t* lo_nodes, int64_t lo_pitch,
+                              const int32_t* start, const int32_t* child, int n_parents, int width, int64_t S,
+                              uint64_t* up_slots, uint32_t* up_nodes, int64_t up_pitch);
+// out[p] and feasible[p][n_levels] for every pick p < P whose shape lies in [s0, s0 + S), from the rows
+// leaf_slots[shape - s0] ([S][size[0]]) and upper_slots[shape - s0] ([S][pitch]; unused at n_levels 1).
+hipError_t launch_tree_select(hipStream_t s, const uint64_t* leaf_slots, const uint64_t* upper_slots, int64_t s0,
+                              int64_t S, const TreeLevels& levels, const TreePick* picks, int64_t P, TreeSel* out,
+                              uint32_t* feasible);
+
 }  // namespace pe

@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -24,7 +24,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain"]
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree"]
 
 
 class PlacementError(RuntimeError):
@@ -97,6 +97,59 @@ def select_domain(dom_slots, count):
     domain = np.where(feasible > 0, masked.argmin(axis=1) if t.shape[1] else 0, -1).astype(np.int32)   # argmin: first of equals
     slots = np.where(feasible > 0, masked.min(axis=1) if t.shape[1] else 0, 0).astype(np.int64)
     return domain, slots, feasible
+
+
+class TreeCapacity(NamedTuple):
+    """Engine.gang_capacity_tree's answer; a part that was not asked for is None.  T = sum(level_size); the
+    column of domain k of level l is sum(level_size[:l]) + k."""
+    tree_slots: Optional[np.ndarray]     # int64 [J][T]: pods of job j's shape that each domain of each level holds
+    tree_nodes: Optional[np.ndarray]     # int64 [J][T]: its nodes holding at least one
+    level: Optional[np.ndarray]          # int32 [J]: lowest level <= max_level with a domain of slots >= count; -1 = none
+    domain: Optional[np.ndarray]         # int32 [J]: that level's domain with the smallest such slots, ties to the smallest id
+    domain_slots: Optional[np.ndarray]   # int64 [J]: that domain's slots, 0 when none
+    feasible: Optional[np.ndarray]       # int32 [J][n_levels]: domains of each level with slots >= count
+
+
+def _level_sizes(level_size):
+    ls = np.asarray(level_size, dtype=np.int64).reshape(-1)
+    if not 1 <= len(ls) <= PE_MAX_LEVELS or (ls < 1).any() or (ls > PE_MAX_DOMAINS).any():
+        raise ValueError("level_size must hold 1 .. PE_MAX_LEVELS sizes in [1, PE_MAX_DOMAINS]")
+    return ls
+
+
+def select_tree(tree_slots, count, level_size, max_level=None):
+    """The selection rule of pe_gang_capacity_tree on a host table: for the shards' tree_slots tables ADDED
+    UP ([J][T]; one shard's table must not be selected from), count [J] >= 1 and max_level [J] in
+    [0, n_levels) (None = the top level), (level int32[J], domain int32[J], domain_slots int64[J], feasible
+    int32[J][n_levels]) -- the lowest level <= max_level at which a domain holds the gang, there the domain
+    with the smallest slots >= count (ties to the smallest id), -1 / -1 / 0 when none, and per level how
+    many domains hold the gang."""
+    ls = _level_sizes(level_size)
+    L = len(ls)
+    t = np.asarray(tree_slots, dtype=np.int64)
+    cnt = np.asarray(count, dtype=np.int64).reshape(-1)
+    J = cnt.shape[0]
+    if t.ndim != 2 or t.shape != (J, int(ls.sum())):
+        raise ValueError("tree_slots must be [J][sum(level_size)] and count [J]")
+    ml = np.full(J, L - 1, dtype=np.int64) if max_level is None else np.asarray(max_level, dtype=np.int64).reshape(-1)
+    if ml.shape != (J,):
+        raise ValueError("max_level must be [J]")
+    if (cnt < 1).any():
+        raise ValueError("count must be >= 1")
+    if ((ml < 0) | (ml >= L)).any():
+        raise ValueError("max_level must be in [0, n_levels)")
+    level = np.full(J, -1, dtype=np.int32)
+    domain = np.full(J, -1, dtype=np.int32)
+    slots = np.zeros(J, dtype=np.int64)
+    feasible = np.zeros((J, L), dtype=np.int32)
+    off = 0
+    for l in range(L):
+        d, s, f = select_domain(t[:, off:off + int(ls[l])], cnt)
+        feasible[:, l] = f
+        take = (level < 0) & (ml >= l) & (f > 0)
+        level[take], domain[take], slots[take] = l, d[take], s[take]
+        off += int(ls[l])
+    return level, domain, slots, feasible
 
 
 def comm_id() -> bytes:
@@ -419,6 +472,52 @@ class Engine:
                                                     _p(domain), _p(domain_slots), _p(feasible)),
                   "pe_gang_capacity_domains")
         return DomainCapacity(dom_slots, dom_nodes, domain, domain_slots, feasible)
+
+    def gang_capacity_tree(self, req, need=None, count=None, max_level=None, level_size=None, parent=None,
+                           tables=True) -> TreeCapacity:
+        """pe_gang_capacity_tree: gang capacity over a hierarchy of topology levels.  level_size [n_levels]
+        (level 0 = the leaf level, the nodes' island ids in [0, level_size[0])); parent [T - level_size[-1]]:
+        parent[off_l + k] = the level-(l + 1) domain holding domain k of level l, or -1 (None allowed with one
+        level).  With tables=True the [J][T] tables tree_slots / tree_nodes come back; with count ([J], >= 1)
+        the device also selects per job the lowest level <= max_level ([J] or None = the top level) at which
+        one domain holds the gang and the best-fitting domain there (level, domain, domain_slots, feasible
+        [J][n_levels]) -- with tables=False nothing but those answers crosses.  On a sharded context only the
+        tables are available: add them over the shards and use select_tree.  Read-only, like gang_capacity."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        L = len(ls)
+        cnt = None if count is None else _c(count, np.int32)
+        if cnt is not None and cnt.shape != (J,):
+            raise ValueError("count must be [J]")
+        ml = None if max_level is None else _c(max_level, np.int32)
+        if ml is not None and ml.shape != (J,):
+            raise ValueError("max_level must be [J]")
+        if ml is not None and cnt is None:
+            raise ValueError("max_level needs count")
+        valid = 1 <= L <= PE_MAX_LEVELS and bool(((ls >= 1) & (ls <= PE_MAX_DOMAINS)).all())
+        T = int(ls.astype(np.int64).sum()) if valid else 0
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        if valid and par is not None and len(par) != T - int(ls[-1]):
+            raise ValueError("parent must be [sum(level_size) - level_size[-1]]")
+        big = tables and valid   # (a hierarchy the engine refuses allocates nothing here)
+        tree_slots = np.zeros((J, T), dtype=np.int64) if big else None
+        tree_nodes = np.zeros((J, T), dtype=np.int64) if big else None
+        sel = cnt is not None
+        level = np.full(J, -1, dtype=np.int32) if sel else None
+        domain = np.full(J, -1, dtype=np.int32) if sel else None
+        domain_slots = np.zeros(J, dtype=np.int64) if sel else None
+        feasible = np.zeros((J, max(L, 1)), dtype=np.int32) if sel else None
+        self._chk(self.lib.pe_gang_capacity_tree(self.h, J, _p(req), _p(nd), _p(cnt), _p(ml), L, _p(ls), _p(par),
+                                                 _p(tree_slots), _p(tree_nodes), _p(level), _p(domain),
+                                                 _p(domain_slots), _p(feasible)),
+                  "pe_gang_capacity_tree")
+        return TreeCapacity(tree_slots, tree_nodes, level, domain, domain_slots, feasible)
 
     # ------------------------------------------------------------ greedy
     def place_greedy(self, job_group_off, priority, group_count, group_req, group_need=None):

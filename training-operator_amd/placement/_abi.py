@@ -26,6 +26,7 @@ PE_COMM_ID_BYTES = 128
 PE_DIMS = 4
 PE_CAP_MAX = 2147483647
 PE_MAX_DOMAINS = 65536
+PE_MAX_LEVELS = 4
 
 ERR_NAMES = {PE_EINVAL: "PE_EINVAL", PE_EOVERFLOW: "PE_EOVERFLOW", PE_ENOMEM: "PE_ENOMEM", PE_EHIP: "PE_EHIP",
              PE_ERCCL: "PE_ERCCL", PE_ESTATE: "PE_ESTATE", PE_ENODEV: "PE_ENODEV"}
@@ -82,6 +83,7 @@ SIGNATURES = {
     "pe_fit_mask": (ctypes.c_int, [P, i64, P, P, P, ctypes.POINTER(P), ctypes.POINTER(i64)]),
     "pe_gang_capacity": (ctypes.c_int, [P, i64, P, P, P, P, P]),
     "pe_gang_capacity_domains": (ctypes.c_int, [P, i64, P, P, P, i32, P, P, P, P, P]),
+    "pe_gang_capacity_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, P, P, P, P, P, P]),
     "pe_jobs_upload": (ctypes.c_int, [P, i64, P, P]),
     "pe_fit_mask_run": (ctypes.c_int, [P]),
     "pe_fit_counts": (ctypes.c_int, [P, P]),
