@@ -7,55 +7,15 @@ in the same process as the yardstick, and the kernels alone (PE_CAP_EVENTS=1: hi
 stream, read back from pe_last_error).  Every step runs under a watchdog of its own that ends the process
 if it overruns.
     python tools/gang_capacity_domains_latency.py      (GC_NODES / GC_JOBS / GC_DOMAINS / GC_STEP_LIMIT_S to resize)"""
-import ctypes
-import faulthandler
 import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "training-operator_amd")]
+from gang_capacity_common import JOBS, NODES, capacity_call, kernel_ms, ptr, step   # (first: it sets the path)
 import bench  # noqa: E402
 from placement import Engine, synth  # noqa: E402
 
-P = ctypes.c_void_p
-LIMIT = int(os.environ.get("GC_STEP_LIMIT_S", "120"))
-NODES = int(os.environ.get("GC_NODES", "1000000"))
-JOBS = int(os.environ.get("GC_JOBS", "100000"))
 DOMAINS = int(os.environ.get("GC_DOMAINS", "4096"))
-
-
-class step:
-    """One GPU step under its own time limit: past it the watchdog thread dumps the stacks and exits."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        print(f"[{self.name}]", flush=True)
-        faulthandler.dump_traceback_later(LIMIT, exit=True)
-
-    def __exit__(self, *exc):
-        faulthandler.cancel_dump_traceback_later()
-        return False
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(P)
-
-
-def capacity_call(eng, req, need):
-    J = req.shape[0]
-    slots, mx, nodes = np.zeros(J, np.int64), np.zeros(J, np.int32), np.zeros(J, np.int64)
-    args = (eng.h, J, ptr(req), ptr(need), ptr(slots), ptr(mx), ptr(nodes))
-
-    def call():
-        rc = eng.lib.pe_gang_capacity(*args)
-        assert rc == 0, eng.lib.pe_last_error(eng.h)
-    call.keep = (req, need, slots, mx, nodes)
-    return call
 
 
 def domains_call(eng, req, need, count):
@@ -68,21 +28,6 @@ def domains_call(eng, req, need, count):
         assert rc == 0, eng.lib.pe_last_error(eng.h)
     call.keep = (req, need, count, dom, slots, feas)
     return call
-
-
-def kernel_ms(eng, call, reps, warm):
-    """Median of the kernels' hipEvent time over `reps` calls (PE_CAP_EVENTS=1)."""
-    os.environ["PE_CAP_EVENTS"] = "1"
-    try:
-        ms = []
-        for i in range(warm + reps):
-            call()
-            m = re.search(r"kernels_ms=([0-9.]+)", eng.lib.pe_last_error(eng.h).decode())
-            if i >= warm:
-                ms.append(float(m.group(1)))
-        return sorted(ms)[len(ms) // 2]
-    finally:
-        del os.environ["PE_CAP_EVENTS"]
 
 
 seed = synth.SEED["cfg5"]
@@ -105,10 +50,10 @@ for name, island in layouts:
             if first > 250e3:   # a slow layout: fewer repetitions, the step stays within its limit
                 reps, warm, kreps = 5, 1, 3
             med, p90 = bench.time_calls(dom, reps, warm)
-            k = kernel_ms(eng, dom, kreps, 2)
+            k, _ = kernel_ms(eng, dom, kreps, 2)
             yard = capacity_call(eng, req[:J], need[:J])
             ymed, yp90 = bench.time_calls(yard, reps, warm)
-            yk = kernel_ms(eng, yard, kreps, 2)
+            yk, _ = kernel_ms(eng, yard, kreps, 2)
             print(f"{name} J {J}: pe_gang_capacity_domains call {med:.1f} us (p90 {p90:.1f}), kernels {k * 1e3:.1f} us; "
                   f"pe_gang_capacity call {ymed:.1f} us (p90 {yp90:.1f}), kernels {yk * 1e3:.1f} us; "
                   f"ratio call {med / ymed:.2f}, kernels {k / yk:.2f}", flush=True)

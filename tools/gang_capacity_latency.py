@@ -6,54 +6,12 @@ capacity kernels alone (PE_CAP_EVENTS=1: hipEvents on the context stream around 
 from pe_last_error).  Every step runs under a watchdog of its own that ends the process if it overruns.
     python tools/gang_capacity_latency.py            (GC_NODES / GC_JOBS / GC_STEP_LIMIT_S to resize)"""
 import ctypes
-import faulthandler
-import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "training-operator_amd")]
+from gang_capacity_common import JOBS, NODES, P, capacity_call, kernel_ms, ptr, step   # (first: it sets the path)
 import bench  # noqa: E402
 from placement import Engine, synth  # noqa: E402
-
-P = ctypes.c_void_p
-LIMIT = int(os.environ.get("GC_STEP_LIMIT_S", "120"))
-NODES = int(os.environ.get("GC_NODES", "1000000"))
-JOBS = int(os.environ.get("GC_JOBS", "100000"))
-
-
-class step:
-    """One GPU step under its own time limit: past it the watchdog thread dumps the stacks and exits."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        print(f"[{self.name}]", flush=True)
-        faulthandler.dump_traceback_later(LIMIT, exit=True)
-
-    def __exit__(self, *exc):
-        faulthandler.cancel_dump_traceback_later()
-        return False
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(P)
-
-
-def capacity_call(eng, req, need):
-    req, need = np.ascontiguousarray(req, np.int64), np.ascontiguousarray(need, np.uint32)
-    J = req.shape[0]
-    slots, mx, nodes = np.zeros(J, np.int64), np.zeros(J, np.int32), np.zeros(J, np.int64)
-    args = (eng.h, J, ptr(req), ptr(need), ptr(slots), ptr(mx), ptr(nodes))
-
-    def call():
-        rc = eng.lib.pe_gang_capacity(*args)
-        assert rc == 0, eng.lib.pe_last_error(eng.h)
-    call.keep = (req, need, slots, mx, nodes)
-    return call
 
 
 def fit_call(eng, req, need):
@@ -66,22 +24,6 @@ def fit_call(eng, req, need):
         assert eng.lib.pe_fit_mask(*args) == 0
     call.keep = (req, need, counts)
     return call
-
-
-def kernel_ms(eng, call, reps, warm):
-    """Median of the kernels' hipEvent time over `reps` calls (PE_CAP_EVENTS=1)."""
-    os.environ["PE_CAP_EVENTS"] = "1"
-    try:
-        ms, shapes = [], None
-        for i in range(warm + reps):
-            call()
-            m = re.match(r"S=(\d+) kernels_ms=([0-9.]+)", eng.lib.pe_last_error(eng.h).decode())
-            shapes = int(m.group(1))
-            if i >= warm:
-                ms.append(float(m.group(2)))
-        return sorted(ms)[len(ms) // 2], shapes
-    finally:
-        del os.environ["PE_CAP_EVENTS"]
 
 
 seed = synth.SEED["cfg5"]

@@ -8,43 +8,15 @@ tree call at n_levels = 1.  Call time, and the kernels alone (PE_CAP_EVENTS=1: h
 stream, read back from pe_last_error).  Every step runs under a watchdog of its own that ends the process
 if it overruns.
     python tools/gang_capacity_tree_latency.py      (GC_NODES / GC_JOBS / GC_RACK / GC_STEP_LIMIT_S to resize)"""
-import ctypes
-import faulthandler
 import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "training-operator_amd")]
+from gang_capacity_common import JOBS, NODES, kernel_ms, ptr, step   # (first: it sets the path)
 import bench  # noqa: E402
 from placement import Engine, synth  # noqa: E402
 
-P = ctypes.c_void_p
-LIMIT = int(os.environ.get("GC_STEP_LIMIT_S", "120"))
-NODES = int(os.environ.get("GC_NODES", "1000000"))
-JOBS = int(os.environ.get("GC_JOBS", "100000"))
 RACK = int(os.environ.get("GC_RACK", "245"))
-
-
-class step:
-    """One GPU step under its own time limit: past it the watchdog thread dumps the stacks and exits."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        print(f"[{self.name}]", flush=True)
-        faulthandler.dump_traceback_later(LIMIT, exit=True)
-
-    def __exit__(self, *exc):
-        faulthandler.cancel_dump_traceback_later()
-        return False
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(P)
 
 
 def domains_call(eng, req, need, count, n_domains):
@@ -74,21 +46,6 @@ def tree_call(eng, req, need, count, sizes, parent):
     return call
 
 
-def kernel_ms(eng, call, reps, warm):
-    """Median of the kernels' hipEvent time over `reps` calls (PE_CAP_EVENTS=1)."""
-    os.environ["PE_CAP_EVENTS"] = "1"
-    try:
-        ms = []
-        for i in range(warm + reps):
-            call()
-            m = re.search(r"kernels_ms=([0-9.]+)", eng.lib.pe_last_error(eng.h).decode())
-            if i >= warm:
-                ms.append(float(m.group(1)))
-        return sorted(ms)[len(ms) // 2]
-    finally:
-        del os.environ["PE_CAP_EVENTS"]
-
-
 seed = synth.SEED["cfg5"]
 inv = synth.make_inventory(NODES, seed, 0.2)
 req, need = synth.make_fit_jobs(JOBS, seed)
@@ -115,7 +72,7 @@ for J, reps, warm, kreps in ((1, 500, 30, 100), (JOBS, 20, 3, 10)):
         got = []
         for name, call in calls:
             med, p90 = bench.time_calls(call, reps, warm)
-            k = kernel_ms(eng, call, kreps, 2)
+            k, _ = kernel_ms(eng, call, kreps, 2)
             got.append((med, k))
             print(f"J {J}: {name} call {med:.1f} us (p90 {p90:.1f}), kernels {k * 1e3:.1f} us", flush=True)
         # the same answers from all three where they overlap

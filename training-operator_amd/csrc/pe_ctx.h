@@ -1,5 +1,6 @@
-// libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp): device and
-// pinned buffers, the helper threads, error mapping and the context itself.  Not part of the ABI.
+// libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
+// pe_engine_capacity.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
+// the context itself.  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -364,9 +365,10 @@ struct pe_ctx {
   DevBuf<uint8_t> aw_dev;
   std::vector<int64_t> aw_jobs, aw_lo;
   std::vector<uint8_t> aw_mark;
-  // gang capacity (pe_gang_capacity): the call's distinct shapes and their results (pinned), the device
-  // copies, the per-node-block partials, the dedupe table and each job's shape.  Grow and are reused;
-  // nothing of the staged fit mask is shared.
+  // gang capacity (pe_engine_capacity.cpp; the shapes, their dedupe and the events serve all three calls):
+  // the call's distinct shapes and pe_gang_capacity's results (pinned), the device copies, the
+  // per-node-block partials, the dedupe table and each job's shape.  Grow and are reused; nothing of the
+  // staged fit mask is shared.
   HostBuf<pe::CapShape> cp_hshapes;
   HostBuf<pe::CapAcc> cp_hout;
   DevBuf<pe::CapShape> cp_shapes;
@@ -374,29 +376,19 @@ struct pe_ctx {
   std::vector<pe::CapShape> cp_uniq;
   std::vector<int32_t> cp_tab, cp_of;
   hipEvent_t cp_ev[2] = {nullptr, nullptr};   // PE_CAP_EVENTS=1: around the call's kernels
-  // gang capacity per domain (pe_gang_capacity_domains; shapes, dedupe and events are cp_*): the device
-  // tables of one chunk of shapes and their pinned copies, the call's distinct (shape, count) picks with
-  // their answers, the pick dedupe table and each job's pick.  Grow and are reused; nothing outlives a call.
-  DevBuf<uint64_t> dm_table;   // per launch of sc shapes: slots u64 [sc][D], then nodes u32 [sc][D]
-  HostBuf<uint64_t> dm_hslots;
-  HostBuf<uint32_t> dm_hnodes;
-  HostBuf<pe::DomPick> dm_hpicks;
-  DevBuf<pe::DomPick> dm_picks;
-  DevBuf<pe::DomSel> dm_sel;
-  HostBuf<pe::DomSel> dm_hsel;
-  std::vector<pe::DomPick> dm_upicks;
-  std::vector<int32_t> dm_ptab, dm_pof;
-  // gang capacity over a hierarchy (pe_gang_capacity_tree; shapes, dedupe and events are cp_*, the leaf table
-  // and the pinned table copies are dm_table / dm_hslots / dm_hnodes, the pick dedupe is dm_ptab / dm_pof --
-  // every call of either entry point sizes and fills what it uses, so the calls may alternate): the upper
-  // levels' table of one chunk of shapes, the call's roll-up plan, its distinct (shape, count, max_level)
-  // picks and their answers.  Grow and are reused; nothing outlives a call.
-  DevBuf<uint64_t> tr_upper;   // per launch of sc shapes: slots u64 [sc][U], then nodes u32 [sc][U]
-  HostBuf<int32_t> tr_hin;     // one copy in: the plan's words, then (16-B aligned) the P picks
-  DevBuf<int32_t> tr_in;
-  DevBuf<uint32_t> tr_out;     // one copy out: P TreeSel records, then the counts [P][n_levels]
-  HostBuf<uint32_t> tr_hout;
-  std::vector<pe::TreePick> tr_upicks;
+  // gang capacity over topology levels (pe_gang_capacity_domains = one level, pe_gang_capacity_tree: one host
+  // path, pe_engine_capacity.cpp capacity_levels; shapes, dedupe and events are cp_*).  Every call sizes and
+  // fills what it uses, so calls of any shape may alternate.  Grow and are reused; nothing outlives a call.
+  DevBuf<uint64_t> lv_leaf;     // per launch of sc shapes: slots u64 [sc][L0], then nodes u32 [sc][L0]
+  DevBuf<uint64_t> lv_upper;    // the same for the U columns of the levels above the leaves
+  HostBuf<uint64_t> lv_hslots;  // a launch's tables on their way out: leaf rows [sc][L0], then upper rows [sc][U]
+  HostBuf<uint32_t> lv_hnodes;
+  HostBuf<int32_t> lv_hin;      // one copy in: the plan's words, then (16-B aligned) the P picks
+  DevBuf<int32_t> lv_in;
+  DevBuf<uint32_t> lv_out;      // one copy out: P TreeSel records, then the counts [P][n_levels]
+  HostBuf<uint32_t> lv_hout;
+  std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
+  std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -468,9 +460,8 @@ struct pe_ctx {
     a_req.release(); a_out.release(); a_fl.release(); a_pres.release(); a_ovf.release();
     aw_stage.release(); aw_outh.release(); aw_dev.release();
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
-    dm_table.release(); dm_hslots.release(); dm_hnodes.release(); dm_hpicks.release();
-    dm_picks.release(); dm_sel.release(); dm_hsel.release();
-    tr_upper.release(); tr_hin.release(); tr_in.release(); tr_out.release(); tr_hout.release();
+    lv_leaf.release(); lv_upper.release(); lv_hslots.release(); lv_hnodes.release();
+    lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release();
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -545,7 +536,41 @@ inline void need_ptr(const void* p, const char* name) {
   if (!p) raise(PE_EINVAL, std::string(name) + " is NULL");
 }
 
-// (pe_engine.cpp: they validate large arrays on its planning pool)
+// pe_engine.cpp's planning pool: f(0) on the caller, f(1 .. n-1) on pool threads; returns when all are
+// done, rethrows the first exception.
+void plan_pool_run(int n, const std::function<void(int)>& f);
+
+// The first index in [0, n) where bad(i) holds, or n: chunks of 4096 reduced branch-free (the
+// loops vectorise), on the planning pool for large arrays (the aggregation validates ~10^7 values
+// per call).
+template <class Bad>
+int64_t first_bad(int64_t n, Bad bad) {
+  constexpr int64_t kChunk = 4096;
+  auto scan = [&](int64_t b, int64_t e) -> int64_t {
+    for (int64_t c = b; c < e; c += kChunk) {
+      const int64_t ce = std::min(e, c + kChunk);
+      bool any = false;
+      for (int64_t i = c; i < ce; ++i) any |= bad(i);
+      if (any)
+        for (int64_t i = c; i < ce; ++i)
+          if (bad(i)) return i;
+    }
+    return e;
+  };
+  if (n < (int64_t(1) << 20)) return scan(0, n);
+  constexpr int kT = 8;
+  int64_t first[kT];
+  plan_pool_run(kT, [&](int t) {
+    const int64_t b = n * t / kT, e = n * (t + 1) / kT;
+    const int64_t r = scan(b, e);
+    first[t] = r < e ? r : n;
+  });
+  int64_t r = n;
+  for (int t = 0; t < kT; ++t) r = std::min(r, first[t]);
+  return r;
+}
+
+// (pe_engine.cpp)
 void check_req(const int64_t* req, int64_t n, const char* what);
 void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* what);
 

@@ -21,14 +21,14 @@
 //   4. Flush: every non-zero accumulator is added to the zeroed global table with one 64-bit and one
 //      32-bit vector atomicAdd (the latter only when the node table is asked for), and zeroed.
 // Integers throughout: the result does not depend on any order.
-// domain_select_kernel: one wave per distinct (shape, count) scans the shape's row of dom_slots for the
-// smallest value >= count (ties: the smallest id) and counts the values >= count.
+// The selection from a table's rows is pe_tree.hip's tree_select_kernel, at one level for this call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "pe_capacity_eval.h"
 #include "pe_kernels.h"
+#include "pe_wave.h"
 
 namespace pe {
 
@@ -54,14 +54,6 @@ __device__ __forceinline__ int uniform_width(int x) {
     w <<= 1;
   }
   return w;
-}
-
-// Sum over each aligned group of w lanes (w a wave-uniform power of two).
-__device__ __forceinline__ uint64_t group_sum_u64(uint64_t v, int w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    if (o < w) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(CP_THREADS) void gang_capacity_domains_kernel(
@@ -175,42 +167,6 @@ __global__ __launch_bounds__(CP_THREADS) void gang_capacity_domains_kernel(
   }
 }
 
-// out[p] for the picks whose shape lies in this launch's rows [s0, s0 + S): one wave per pick.
-__global__ __launch_bounds__(256) void domain_select_kernel(const unsigned long long* __restrict__ dom_slots, int s0,
-                                                            int S, int n_domains, const DomPick* __restrict__ picks,
-                                                            int P, DomSel* __restrict__ out) {
-  const int p = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (p >= P) return;
-  const DomPick pk = picks[p];
-  const int64_t s = (int64_t)pk.shape - s0;
-  if (s < 0 || s >= S) return;   // a row of another launch
-  const unsigned long long* row = dom_slots + s * n_domains;
-  const uint64_t count = (uint64_t)pk.count;   // >= 1
-  uint64_t best = ~uint64_t(0);
-  uint32_t bk = ~0u, feas = 0;
-  for (int k = lane; k < n_domains; k += 64) {
-    const uint64_t x = row[k];
-    if (x >= count) {
-      ++feas;
-      if (x < best) {   // k ascends: the first of equal values stays
-        best = x;
-        bk = (uint32_t)k;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t ob = __shfl_xor(best, o, 64);
-    const uint32_t ok = __shfl_xor(bk, o, 64);
-    feas += __shfl_xor(feas, o, 64);
-    if (ob < best || (ob == best && ok < bk)) {
-      best = ob;
-      bk = ok;
-    }
-  }
-  if (lane == 0) out[p] = DomSel{bk == ~0u ? 0 : best, (int32_t)bk, feas};   // none: 0, -1, 0
-}
-
 }  // namespace
 
 hipError_t launch_gang_capacity_domains(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
@@ -225,14 +181,6 @@ hipError_t launch_gang_capacity_domains(hipStream_t s, const int64_t* res, int64
   hipLaunchKernelGGL(gang_capacity_domains_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(CP_THREADS), 0, s, res,
                      stride, labels, island, Ns, shapes, (int)S, (int)spb, n_domains, (unsigned long long*)dom_slots,
                      dom_nodes);
-  return hipGetLastError();
-}
-
-hipError_t launch_domain_select(hipStream_t s, const uint64_t* dom_slots, int64_t s0, int64_t S, int n_domains,
-                                const DomPick* picks, int64_t P, DomSel* out) {
-  if (P <= 0 || S <= 0) return hipSuccess;
-  hipLaunchKernelGGL(domain_select_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s,
-                     (const unsigned long long*)dom_slots, (int)s0, (int)S, n_domains, picks, (int)P, out);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // libplacement: context, device-resident inventory, C ABI entry points (include/placement.h) -- all but
-// the greedy placement, which is pe_engine_greedy.cpp; the context itself is pe_ctx.h.
+// the greedy placement, which is pe_engine_greedy.cpp, and the gang-capacity calls, which are
+// pe_engine_capacity.cpp; the context itself is pe_ctx.h.
 //
 // One context = one process = one GPU = one contiguous shard of the node inventory.  The
 // inventory lives on the device as int64 struct-of-arrays res[4][stride] (+ labels, islands),
@@ -31,11 +32,9 @@
 #include <vector>
 
 #include "pe_ctx.h"
-#include "pe_divmagic.h"
 #include "pe_hostx.h"
 #include "pe_kernels.h"
 #include "pe_resolver.h"
-#include "pe_tree_plan.h"
 #include "placement.h"
 
 namespace {
@@ -204,39 +203,11 @@ class PlanPool {
   std::atomic<uint64_t> agen_{0};   // gen_, for the spinning workers (written under mu_)
 };
 
-// The first index in [0, n) where bad(i) holds, or n: chunks of 4096 reduced branch-free (the
-// loops vectorise), on the planning pool for large arrays (the aggregation validates ~10^7 values
-// per call).
-template <class Bad>
-int64_t first_bad(int64_t n, Bad bad) {
-  constexpr int64_t kChunk = 4096;
-  auto scan = [&](int64_t b, int64_t e) -> int64_t {
-    for (int64_t c = b; c < e; c += kChunk) {
-      const int64_t ce = std::min(e, c + kChunk);
-      bool any = false;
-      for (int64_t i = c; i < ce; ++i) any |= bad(i);
-      if (any)
-        for (int64_t i = c; i < ce; ++i)
-          if (bad(i)) return i;
-    }
-    return e;
-  };
-  if (n < (int64_t(1) << 20)) return scan(0, n);
-  constexpr int kT = 8;
-  int64_t first[kT];
-  PlanPool::get().run(kT, [&](int t) {
-    const int64_t b = n * t / kT, e = n * (t + 1) / kT;
-    const int64_t r = scan(b, e);
-    first[t] = r < e ? r : n;
-  });
-  int64_t r = n;
-  for (int t = 0; t < kT; ++t) r = std::min(r, first[t]);
-  return r;
-}
-
 }  // namespace
 
 namespace pe_engine {
+
+void plan_pool_run(int n, const std::function<void(int)>& f) { PlanPool::get().run(n, f); }
 
 void check_req(const int64_t* req, int64_t n, const char* what) {
   const int64_t i = first_bad(n * pe::D, [req](int64_t k) { return req[k] < 0; });
@@ -2192,511 +2163,6 @@ int pe_fit_mask(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t*
     else hipchk(hipStreamSynchronize(ctx->stream), "sync fit");
     if (dev_mask) *dev_mask = ctx->mask.p;
     if (words_per_row) *words_per_row = ctx->Wn;
-    return PE_OK;
-  });
-}
-
-// The batch's distinct (request, need) shapes in first-seen order -> ctx->cp_uniq (with the reciprocals of
-// their requests), each job's shape -> ctx->cp_of; returns their number.  Shared by pe_gang_capacity and
-// pe_gang_capacity_domains.
-static int64_t cap_dedupe(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need) {
-  // distinct shapes, in first-seen order (open addressing; a job equal to its predecessor skips the probe)
-  auto& uniq = ctx->cp_uniq;
-  auto& of = ctx->cp_of;
-  auto& tab = ctx->cp_tab;
-  uniq.clear();
-  of.resize((size_t)n_jobs);
-  size_t cap = 16;
-  while (cap < (size_t)n_jobs * 2) cap <<= 1;
-  tab.assign(cap, -1);
-  auto same = [&](const pe::CapShape& s, const int64_t* q, uint32_t nd) {
-    return s.q[0] == q[0] && s.q[1] == q[1] && s.q[2] == q[2] && s.q[3] == q[3] && s.need == nd;
-  };
-  for (int64_t j = 0; j < n_jobs; ++j) {
-    const int64_t* q = req + j * pe::D;
-    const uint32_t nd = need ? need[j] : 0u;
-    if (j > 0 && same(uniq[(size_t)of[(size_t)j - 1]], q, nd)) {
-      of[(size_t)j] = of[(size_t)j - 1];
-      continue;
-    }
-    uint64_t h = nd;
-    for (int d = 0; d < pe::D; ++d) {
-      h = (h ^ (uint64_t)q[d]) * 0x9E3779B97F4A7C15ull;
-      h ^= h >> 29;
-    }
-    size_t at = (size_t)h & (cap - 1);
-    while (tab[at] >= 0 && !same(uniq[(size_t)tab[at]], q, nd)) at = (at + 1) & (cap - 1);
-    if (tab[at] < 0) {
-      tab[at] = (int32_t)uniq.size();
-      pe::CapShape sp{};
-      for (int d = 0; d < pe::D; ++d) {
-        sp.q[d] = q[d];
-        if (q[d] > 0) {
-          const pe::DivMagic dm = pe::div_magic((uint64_t)q[d]);
-          sp.m[d] = dm.m;
-          sp.sh[d] = dm.shift;
-        }
-      }
-      sp.need = nd;
-      uniq.push_back(sp);
-    }
-    of[(size_t)j] = tab[at];
-  }
-  return (int64_t)uniq.size();
-}
-
-// Gang capacity: the distinct (request, need) shapes of the batch go to the device with the
-// reciprocals of their requests (pe_divmagic.h), gang_capacity_kernel answers per shape over the
-// shard's current residuals, and the host scatters the answers back to the jobs.  Own buffers: the
-// staged fit-mask state is not touched.  PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity_latency.py):
-// hipEvents around the kernels; a successful call then leaves "S=<shapes> kernels_ms=<time>" in
-// pe_last_error.
-int pe_gang_capacity(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, int64_t* out_slots,
-                     int32_t* out_max_node, int64_t* out_nodes) {
-  return guarded(ctx, [&]() -> int {
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    if (n_jobs == 0) return PE_OK;
-    if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
-    need_ptr(req, "req");
-    check_req(req, n_jobs, "req");
-    const int64_t S = cap_dedupe(ctx, n_jobs, req, need);
-    const auto& uniq = ctx->cp_uniq;
-    const auto& of = ctx->cp_of;
-    const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
-    float kernel_ms = 0.f;
-    hipchk(ctx->cp_hout.ensure((size_t)S), "alloc pinned capacity results");
-    if (ctx->Ns == 0) {   // an empty shard holds nothing
-      std::memset((void*)ctx->cp_hout.p, 0, (size_t)S * sizeof(pe::CapAcc));
-    } else {
-      hipchk(ctx->cp_hshapes.ensure((size_t)S), "alloc pinned shapes");
-      hipchk(ctx->cp_shapes.ensure((size_t)S), "alloc shapes");
-      hipchk(ctx->cp_out.ensure((size_t)S), "alloc capacity results");
-      std::memcpy((void*)ctx->cp_hshapes.p, uniq.data(), (size_t)S * sizeof(pe::CapShape));
-      // shapes per launch: the partials (one record per node block and shape) stay within 64 MiB
-      const int64_t gx = pe::cap_node_blocks(ctx->Ns);
-      const int64_t fit64 = (int64_t(4) << 20) / gx / pe::CP_TS * pe::CP_TS;
-      const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(pe::CP_TS, fit64));
-      hipchk(ctx->cp_part.ensure((size_t)(gx * chunk)), "alloc capacity partials");
-      hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)S * sizeof(pe::CapShape), hipMemcpyHostToDevice,
-                            ctx->stream),
-             "H2D shapes");
-      if (events) {
-        for (hipEvent_t& e : ctx->cp_ev)
-          if (!e) hipchk(hipEventCreate(&e), "event create");
-        hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
-      }
-      for (int64_t s0 = 0; s0 < S; s0 += chunk)
-        hipchk(pe::launch_gang_capacity(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->Ns, ctx->cp_shapes.p + s0,
-                                        std::min(chunk, S - s0), ctx->cp_part.p, ctx->cp_out.p + s0),
-               "launch gang_capacity");
-      if (events) hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
-      hipchk(hipMemcpyAsync(ctx->cp_hout.p, ctx->cp_out.p, (size_t)S * sizeof(pe::CapAcc), hipMemcpyDeviceToHost,
-                            ctx->stream),
-             "D2H capacity results");
-      hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity");
-      if (events) hipchk(hipEventElapsedTime(&kernel_ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
-    }
-    const pe::CapAcc* a = ctx->cp_hout.p;
-    for (int64_t j = 0; j < n_jobs; ++j) {
-      const pe::CapAcc& r = a[of[(size_t)j]];
-      if (out_slots) out_slots[j] = (int64_t)r.slots;
-      if (out_max_node) out_max_node[j] = (int32_t)r.max_node;
-      if (out_nodes) out_nodes[j] = (int64_t)r.nodes;
-    }
-    if (events) ctx->err = "S=" + std::to_string(S) + " kernels_ms=" + std::to_string(kernel_ms);
-    return PE_OK;
-  });
-}
-
-// Gang capacity per topology domain: pe_gang_capacity's distinct shapes (cap_dedupe) go to the device,
-// gang_capacity_domains_kernel adds every node's capacity to the [shape][domain] tables of its island id
-// (pe_domains.hip) and, for a selection, domain_select_kernel answers each distinct (shape, count) from the
-// shape's row, so only J-sized results cross.  The tables exist on the device for one chunk of shapes at a
-// time (64 MiB at most); a requested table is copied out per chunk and scattered to the jobs here.
-// Nothing is kept between calls, and neither the residuals nor the staged fit-mask state are touched.
-// PE_CAP_EVENTS=1: as pe_gang_capacity.
-int pe_gang_capacity_domains(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, const int32_t* count,
-                             int32_t n_domains, int64_t* out_dom_slots, int64_t* out_dom_nodes, int32_t* out_domain,
-                             int64_t* out_domain_slots, int32_t* out_feasible) {
-  return guarded(ctx, [&]() -> int {
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
-    if (n_domains < 1 || n_domains > PE_MAX_DOMAINS) raise(PE_EINVAL, "n_domains outside [1, PE_MAX_DOMAINS]");
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    const bool select = out_domain || out_domain_slots || out_feasible;
-    const bool tables = out_dom_slots || out_dom_nodes;
-    if (select && ctx->world > 1)
-      raise(PE_EINVAL, "selection outputs on a sharded context: a domain may span shards (add the tables, then select)");
-    if (n_jobs == 0) return PE_OK;
-    if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
-    need_ptr(req, "req");
-    check_req(req, n_jobs, "req");
-    if (select) {
-      need_ptr(count, "count");
-      const int64_t i = first_bad(n_jobs, [count](int64_t k) { return count[k] < 1; });
-      if (i < n_jobs) raise(PE_EINVAL, "count: value below 1 at index " + std::to_string(i));
-    }
-    const int64_t Dn = n_domains;
-    if (ctx->Ns == 0) {   // an empty shard holds nothing
-      if (out_dom_slots) std::memset(out_dom_slots, 0, (size_t)(n_jobs * Dn) * sizeof(int64_t));
-      if (out_dom_nodes) std::memset(out_dom_nodes, 0, (size_t)(n_jobs * Dn) * sizeof(int64_t));
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        if (out_domain) out_domain[j] = -1;
-        if (out_domain_slots) out_domain_slots[j] = 0;
-        if (out_feasible) out_feasible[j] = 0;
-      }
-      return PE_OK;
-    }
-    const int64_t S = cap_dedupe(ctx, n_jobs, req, need);
-    const auto& of = ctx->cp_of;
-    // distinct (shape, count) picks, in first-seen order
-    auto& picks = ctx->dm_upicks;
-    auto& pof = ctx->dm_pof;
-    picks.clear();
-    if (select) {
-      auto& tab = ctx->dm_ptab;
-      pof.resize((size_t)n_jobs);
-      size_t cap = 16;
-      while (cap < (size_t)n_jobs * 2) cap <<= 1;
-      tab.assign(cap, -1);
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        const uint32_t sh = (uint32_t)of[(size_t)j];
-        const int32_t c = count[j];
-        if (j > 0 && picks[(size_t)pof[(size_t)j - 1]].shape == sh && picks[(size_t)pof[(size_t)j - 1]].count == c) {
-          pof[(size_t)j] = pof[(size_t)j - 1];
-          continue;
-        }
-        uint64_t h = (((uint64_t)sh << 32) | (uint32_t)c) * 0x9E3779B97F4A7C15ull;
-        h ^= h >> 29;
-        size_t at = (size_t)h & (cap - 1);
-        while (tab[at] >= 0 && !(picks[(size_t)tab[at]].shape == sh && picks[(size_t)tab[at]].count == c))
-          at = (at + 1) & (cap - 1);
-        if (tab[at] < 0) {
-          tab[at] = (int32_t)picks.size();
-          picks.push_back(pe::DomPick{sh, c});
-        }
-        pof[(size_t)j] = tab[at];
-      }
-    }
-    const int64_t P = (int64_t)picks.size();
-    const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
-    float kernel_ms = 0.f;
-    hipchk(ctx->cp_hshapes.ensure((size_t)S), "alloc pinned shapes");
-    hipchk(ctx->cp_shapes.ensure((size_t)S), "alloc shapes");
-    std::memcpy((void*)ctx->cp_hshapes.p, ctx->cp_uniq.data(), (size_t)S * sizeof(pe::CapShape));
-    // shapes per launch: the two tables (12 B per shape and domain) stay within 64 MiB (16 shapes at least)
-    const int64_t fit64 = (int64_t(64) << 20) / (12 * Dn);
-    const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(16, fit64));
-    hipchk(ctx->dm_table.ensure((size_t)(chunk * Dn + (chunk * Dn + 1) / 2)), "alloc domain tables");
-    if (out_dom_slots) hipchk(ctx->dm_hslots.ensure((size_t)(chunk * Dn)), "alloc pinned domain slots");
-    if (out_dom_nodes) hipchk(ctx->dm_hnodes.ensure((size_t)(chunk * Dn)), "alloc pinned domain nodes");
-    hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)S * sizeof(pe::CapShape), hipMemcpyHostToDevice,
-                          ctx->stream),
-           "H2D shapes");
-    if (select) {
-      hipchk(ctx->dm_hpicks.ensure((size_t)P), "alloc pinned picks");
-      hipchk(ctx->dm_picks.ensure((size_t)P), "alloc picks");
-      hipchk(ctx->dm_sel.ensure((size_t)P), "alloc selections");
-      hipchk(ctx->dm_hsel.ensure((size_t)P), "alloc pinned selections");
-      std::memcpy((void*)ctx->dm_hpicks.p, picks.data(), (size_t)P * sizeof(pe::DomPick));
-      hipchk(hipMemcpyAsync(ctx->dm_picks.p, ctx->dm_hpicks.p, (size_t)P * sizeof(pe::DomPick), hipMemcpyHostToDevice,
-                            ctx->stream),
-             "H2D picks");
-    }
-    if (events) {
-      for (hipEvent_t& e : ctx->cp_ev)
-        if (!e) hipchk(hipEventCreate(&e), "event create");
-      hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
-    }
-    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-      const int64_t sc = std::min(chunk, S - s0);
-      // the launch's two tables, adjacent: one memset.  The node table exists only for a caller who reads it
-      // (the selection reads the slots alone): without it the flush costs half the global atomics.
-      uint64_t* const d_slots = ctx->dm_table.p;
-      uint32_t* const d_nodes = out_dom_nodes ? (uint32_t*)(d_slots + sc * Dn) : nullptr;
-      hipchk(hipMemsetAsync(d_slots, 0, (size_t)(sc * Dn) * (sizeof(uint64_t) + (d_nodes ? sizeof(uint32_t) : 0)),
-                            ctx->stream),
-             "zero domain tables");
-      hipchk(pe::launch_gang_capacity_domains(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
-                                              ctx->cp_shapes.p + s0, sc, n_domains, d_slots, d_nodes),
-             "launch gang_capacity_domains");
-      if (select)
-        hipchk(pe::launch_domain_select(ctx->stream, d_slots, s0, sc, n_domains, ctx->dm_picks.p, P,
-                                        ctx->dm_sel.p),
-               "launch domain_select");
-      if (!tables) continue;
-      if (out_dom_slots)
-        hipchk(hipMemcpyAsync(ctx->dm_hslots.p, d_slots, (size_t)(sc * Dn) * sizeof(uint64_t),
-                              hipMemcpyDeviceToHost, ctx->stream),
-               "D2H domain slots");
-      if (out_dom_nodes)
-        hipchk(hipMemcpyAsync(ctx->dm_hnodes.p, d_nodes, (size_t)(sc * Dn) * sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, ctx->stream),
-               "D2H domain nodes");
-      hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_domains");
-      for (int64_t j = 0; j < n_jobs; ++j) {   // the chunk's rows to their jobs
-        const int64_t s = (int64_t)of[(size_t)j] - s0;
-        if (s < 0 || s >= sc) continue;
-        if (out_dom_slots)   // below 2^55: the bits are the int64's
-          std::memcpy(out_dom_slots + j * Dn, (const void*)(ctx->dm_hslots.p + s * Dn), (size_t)Dn * sizeof(int64_t));
-        if (out_dom_nodes) {
-          const uint32_t* row = ctx->dm_hnodes.p + s * Dn;
-          int64_t* o = out_dom_nodes + j * Dn;
-          for (int64_t k = 0; k < Dn; ++k) o[k] = (int64_t)row[k];
-        }
-      }
-    }
-    if (events) hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
-    if (select)
-      hipchk(hipMemcpyAsync(ctx->dm_hsel.p, ctx->dm_sel.p, (size_t)P * sizeof(pe::DomSel), hipMemcpyDeviceToHost,
-                            ctx->stream),
-             "D2H selections");
-    hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_domains");
-    if (events) hipchk(hipEventElapsedTime(&kernel_ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
-    if (select) {
-      const pe::DomSel* a = ctx->dm_hsel.p;
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        const pe::DomSel& r = a[pof[(size_t)j]];
-        if (out_domain) out_domain[j] = r.domain;
-        if (out_domain_slots) out_domain_slots[j] = (int64_t)r.slots;
-        if (out_feasible) out_feasible[j] = (int32_t)r.feasible;
-      }
-    }
-    if (events)
-      ctx->err = "S=" + std::to_string(S) + " P=" + std::to_string(P) + " kernels_ms=" + std::to_string(kernel_ms);
-    return PE_OK;
-  });
-}
-
-static_assert(pe::TREE_MAX_LEVELS == PE_MAX_LEVELS && pe::TR_MAX_LEVELS == PE_MAX_LEVELS, "PE_MAX_LEVELS");
-static_assert(pe::TREE_MAX_LEVEL_SIZE == PE_MAX_DOMAINS, "PE_MAX_DOMAINS");
-
-// Gang capacity over a topology hierarchy: pe_gang_capacity_domains' leaf table (the same kernel, into a
-// [shapes][level_size[0]] table) rolled up on the device along the call's parent map -- one
-// tree_rollup_kernel launch per upper level, into a table of the upper levels' columns -- and, for a
-// selection, tree_select_kernel answering each distinct (shape, count, max_level) from the shape's rows
-// (pe_tree.hip).  The parent map is validated and turned into per-level child lists by pe_tree_plan.h and
-// uploaded once per call; nothing of it is kept.  Both tables exist on the device for one chunk of shapes
-// at a time (12 B per shape and column, 64 MiB at most, 16 shapes at least); requested tables are copied
-// out per chunk and scattered to the jobs here, otherwise only the picks' answers and their per-level
-// counts cross.  Neither the residuals nor the staged fit-mask state are touched.  PE_CAP_EVENTS=1: as
-// pe_gang_capacity.
-int pe_gang_capacity_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, const int32_t* count,
-                          const int32_t* max_level, int32_t n_levels, const int32_t* level_size, const int32_t* parent,
-                          int64_t* out_tree_slots, int64_t* out_tree_nodes, int32_t* out_level, int32_t* out_domain,
-                          int64_t* out_domain_slots, int32_t* out_feasible) {
-  return guarded(ctx, [&]() -> int {
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
-    pe::TreePlan plan;
-    int64_t bad = -1;
-    switch (pe::tree_plan_build(plan, n_levels, level_size, parent, &bad)) {
-      case pe::TREE_OK: break;
-      case pe::TREE_BAD_LEVELS: raise(PE_EINVAL, "n_levels outside [1, PE_MAX_LEVELS]");
-      case pe::TREE_NO_SIZES: raise(PE_EINVAL, "level_size is NULL");
-      case pe::TREE_BAD_SIZE:
-        raise(PE_EINVAL, "level_size: value outside [1, PE_MAX_DOMAINS] at index " + std::to_string(bad));
-      case pe::TREE_NO_PARENT: raise(PE_EINVAL, "parent is NULL with n_levels > 1");
-      case pe::TREE_BAD_PARENT:
-        raise(PE_EINVAL, "parent: value outside [-1, size of the level above) at index " + std::to_string(bad));
-    }
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    const bool select = out_level || out_domain || out_domain_slots || out_feasible;
-    const bool tables = out_tree_slots || out_tree_nodes;
-    if (select && ctx->world > 1)
-      raise(PE_EINVAL, "selection outputs on a sharded context: a domain may span shards (add the tables, then select)");
-    if (n_jobs == 0) return PE_OK;
-    if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
-    need_ptr(req, "req");
-    check_req(req, n_jobs, "req");
-    if (select) {
-      need_ptr(count, "count");
-      int64_t i = first_bad(n_jobs, [count](int64_t k) { return count[k] < 1; });
-      if (i < n_jobs) raise(PE_EINVAL, "count: value below 1 at index " + std::to_string(i));
-      if (max_level) {
-        i = first_bad(n_jobs, [max_level, n_levels](int64_t k) { return max_level[k] < 0 || max_level[k] >= n_levels; });
-        if (i < n_jobs) raise(PE_EINVAL, "max_level: value outside [0, n_levels) at index " + std::to_string(i));
-      }
-    }
-    const int64_t T = plan.columns(), L0 = plan.size[0], U = plan.upper_columns();
-    if (ctx->Ns == 0) {   // an empty shard holds nothing
-      if (out_tree_slots) std::memset(out_tree_slots, 0, (size_t)(n_jobs * T) * sizeof(int64_t));
-      if (out_tree_nodes) std::memset(out_tree_nodes, 0, (size_t)(n_jobs * T) * sizeof(int64_t));
-      if (out_feasible) std::memset(out_feasible, 0, (size_t)(n_jobs * n_levels) * sizeof(int32_t));
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        if (out_level) out_level[j] = -1;
-        if (out_domain) out_domain[j] = -1;
-        if (out_domain_slots) out_domain_slots[j] = 0;
-      }
-      return PE_OK;
-    }
-    const int64_t S = cap_dedupe(ctx, n_jobs, req, need);
-    const auto& of = ctx->cp_of;
-    // distinct (shape, count, max_level) picks, in first-seen order
-    auto& picks = ctx->tr_upicks;
-    auto& pof = ctx->dm_pof;
-    picks.clear();
-    if (select) {
-      auto& tab = ctx->dm_ptab;
-      pof.resize((size_t)n_jobs);
-      size_t cap = 16;
-      while (cap < (size_t)n_jobs * 2) cap <<= 1;
-      tab.assign(cap, -1);
-      auto same = [](const pe::TreePick& a, uint32_t sh, int32_t c, int32_t ml) {
-        return a.shape == sh && a.count == c && a.max_level == ml;
-      };
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        const uint32_t sh = (uint32_t)of[(size_t)j];
-        const int32_t c = count[j];
-        const int32_t ml = max_level ? max_level[j] : n_levels - 1;
-        if (j > 0 && same(picks[(size_t)pof[(size_t)j - 1]], sh, c, ml)) {
-          pof[(size_t)j] = pof[(size_t)j - 1];
-          continue;
-        }
-        uint64_t h = ((((uint64_t)sh << 32) | (uint32_t)c) ^ ((uint64_t)ml << 61)) * 0x9E3779B97F4A7C15ull;
-        h ^= h >> 29;
-        size_t at = (size_t)h & (cap - 1);
-        while (tab[at] >= 0 && !same(picks[(size_t)tab[at]], sh, c, ml)) at = (at + 1) & (cap - 1);
-        if (tab[at] < 0) {
-          tab[at] = (int32_t)picks.size();
-          picks.push_back(pe::TreePick{sh, c, ml, 0});
-        }
-        pof[(size_t)j] = tab[at];
-      }
-    }
-    const int64_t P = (int64_t)picks.size();
-    const bool events = std::getenv("PE_CAP_EVENTS") != nullptr;
-    float kernel_ms = 0.f;
-    hipchk(ctx->cp_hshapes.ensure((size_t)S), "alloc pinned shapes");
-    hipchk(ctx->cp_shapes.ensure((size_t)S), "alloc shapes");
-    std::memcpy((void*)ctx->cp_hshapes.p, ctx->cp_uniq.data(), (size_t)S * sizeof(pe::CapShape));
-    // shapes per launch: the tables of all levels (12 B per shape and column) stay within 64 MiB (16 shapes at least)
-    const int64_t fit64 = (int64_t(64) << 20) / (12 * T);
-    const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(16, fit64));
-    hipchk(ctx->dm_table.ensure((size_t)(chunk * L0 + (chunk * L0 + 1) / 2)), "alloc leaf tables");
-    if (U > 0) hipchk(ctx->tr_upper.ensure((size_t)(chunk * U + (chunk * U + 1) / 2)), "alloc upper tables");
-    if (out_tree_slots) hipchk(ctx->dm_hslots.ensure((size_t)(chunk * T)), "alloc pinned tree slots");
-    if (out_tree_nodes) hipchk(ctx->dm_hnodes.ensure((size_t)(chunk * T)), "alloc pinned tree nodes");
-    hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)S * sizeof(pe::CapShape), hipMemcpyHostToDevice,
-                          ctx->stream),
-           "H2D shapes");
-    // the call's inputs beside the shapes, in one pinned block and one copy: the plan's words, then the picks
-    const size_t words = plan.words.size(), pick_at = (words + 3) / 4 * 4;   // picks 16-B aligned
-    const size_t in_words = pick_at + (size_t)P * (sizeof(pe::TreePick) / sizeof(int32_t));
-    if (in_words > 0) {
-      hipchk(ctx->tr_hin.ensure(in_words), "alloc pinned plan and picks");
-      hipchk(ctx->tr_in.ensure(in_words), "alloc plan and picks");
-      if (words) std::memcpy((void*)ctx->tr_hin.p, plan.words.data(), words * sizeof(int32_t));
-      if (P) std::memcpy((void*)(ctx->tr_hin.p + pick_at), picks.data(), (size_t)P * sizeof(pe::TreePick));
-      hipchk(hipMemcpyAsync(ctx->tr_in.p, ctx->tr_hin.p, in_words * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream),
-             "H2D plan and picks");
-    }
-    const int32_t* const d_plan = ctx->tr_in.p;
-    const pe::TreePick* const d_picks = (const pe::TreePick*)(ctx->tr_in.p + pick_at);
-    // the answers likewise: P selections, then their [P][n_levels] counts (one copy back)
-    const size_t out_words = (size_t)P * (sizeof(pe::TreeSel) / sizeof(uint32_t)) + (size_t)(P * n_levels);
-    if (select) {
-      hipchk(ctx->tr_out.ensure(out_words), "alloc selections");
-      hipchk(ctx->tr_hout.ensure(out_words), "alloc pinned selections");
-    }
-    pe::TreeSel* const d_sel = (pe::TreeSel*)ctx->tr_out.p;
-    uint32_t* const d_feas = ctx->tr_out.p + (size_t)P * (sizeof(pe::TreeSel) / sizeof(uint32_t));
-    pe::TreeLevels lv{};
-    lv.n_levels = n_levels;
-    lv.pitch = (int32_t)U;
-    for (int l = 0; l < n_levels; ++l) {
-      lv.size[l] = plan.size[l];
-      lv.col[l] = l == 0 ? 0 : plan.off[l] - plan.size[0];
-    }
-    if (events) {
-      for (hipEvent_t& e : ctx->cp_ev)
-        if (!e) hipchk(hipEventCreate(&e), "event create");
-      hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
-    }
-    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-      const int64_t sc = std::min(chunk, S - s0);
-      // the leaf tables as pe_gang_capacity_domains lays them out (adjacent: one memset); the node tables
-      // exist only for a caller who reads them
-      uint64_t* const d_slots = ctx->dm_table.p;
-      uint32_t* const d_nodes = out_tree_nodes ? (uint32_t*)(d_slots + sc * L0) : nullptr;
-      uint64_t* const u_slots = U > 0 ? ctx->tr_upper.p : nullptr;
-      uint32_t* const u_nodes = U > 0 && out_tree_nodes ? (uint32_t*)(u_slots + sc * U) : nullptr;
-      hipchk(hipMemsetAsync(d_slots, 0, (size_t)(sc * L0) * (sizeof(uint64_t) + (d_nodes ? sizeof(uint32_t) : 0)),
-                            ctx->stream),
-             "zero leaf tables");
-      hipchk(pe::launch_gang_capacity_domains(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
-                                              ctx->cp_shapes.p + s0, sc, (int)L0, d_slots, d_nodes),
-             "launch gang_capacity_domains");
-      for (int l = 1; l < n_levels; ++l) {   // level l from level l - 1; every cell of the upper table is stored
-        const bool leaf = l == 1;
-        const int64_t lo_col = leaf ? 0 : lv.col[l - 1];
-        hipchk(pe::launch_tree_rollup(ctx->stream, (leaf ? d_slots : u_slots) + lo_col,
-                                      out_tree_nodes ? (leaf ? d_nodes : u_nodes) + lo_col : nullptr, leaf ? L0 : U,
-                                      d_plan + plan.start_at[l], d_plan + plan.child_at[l], plan.size[l],
-                                      plan.width[l], sc, u_slots + lv.col[l], u_nodes ? u_nodes + lv.col[l] : nullptr, U),
-               "launch tree_rollup");
-      }
-      if (select)
-        hipchk(pe::launch_tree_select(ctx->stream, d_slots, u_slots, s0, sc, lv, d_picks, P, d_sel, d_feas),
-               "launch tree_select");
-      if (!tables) continue;
-      // pinned copies: the chunk's leaf rows [sc][L0], then its upper rows [sc][U]
-      if (out_tree_slots) {
-        hipchk(hipMemcpyAsync(ctx->dm_hslots.p, d_slots, (size_t)(sc * L0) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              ctx->stream),
-               "D2H leaf slots");
-        if (U > 0)
-          hipchk(hipMemcpyAsync(ctx->dm_hslots.p + sc * L0, u_slots, (size_t)(sc * U) * sizeof(uint64_t),
-                                hipMemcpyDeviceToHost, ctx->stream),
-                 "D2H upper slots");
-      }
-      if (out_tree_nodes) {
-        hipchk(hipMemcpyAsync(ctx->dm_hnodes.p, d_nodes, (size_t)(sc * L0) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              ctx->stream),
-               "D2H leaf nodes");
-        if (U > 0)
-          hipchk(hipMemcpyAsync(ctx->dm_hnodes.p + sc * L0, u_nodes, (size_t)(sc * U) * sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, ctx->stream),
-                 "D2H upper nodes");
-      }
-      hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_tree");
-      for (int64_t j = 0; j < n_jobs; ++j) {   // the chunk's rows to their jobs
-        const int64_t s = (int64_t)of[(size_t)j] - s0;
-        if (s < 0 || s >= sc) continue;
-        if (out_tree_slots) {   // below 2^55: the bits are the int64's
-          int64_t* o = out_tree_slots + j * T;
-          std::memcpy(o, (const void*)(ctx->dm_hslots.p + s * L0), (size_t)L0 * sizeof(int64_t));
-          if (U > 0) std::memcpy(o + L0, (const void*)(ctx->dm_hslots.p + sc * L0 + s * U), (size_t)U * sizeof(int64_t));
-        }
-        if (out_tree_nodes) {
-          int64_t* o = out_tree_nodes + j * T;
-          const uint32_t* lrow = ctx->dm_hnodes.p + s * L0;
-          for (int64_t k = 0; k < L0; ++k) o[k] = (int64_t)lrow[k];
-          const uint32_t* urow = ctx->dm_hnodes.p + sc * L0 + s * U;
-          for (int64_t k = 0; k < U; ++k) o[L0 + k] = (int64_t)urow[k];
-        }
-      }
-    }
-    if (events) hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
-    if (select)
-      hipchk(hipMemcpyAsync(ctx->tr_hout.p, ctx->tr_out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
-             "D2H selections");
-    hipchk(hipStreamSynchronize(ctx->stream), "sync gang_capacity_tree");
-    if (events) hipchk(hipEventElapsedTime(&kernel_ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
-    if (select) {
-      const pe::TreeSel* a = (const pe::TreeSel*)ctx->tr_hout.p;
-      const uint32_t* f = ctx->tr_hout.p + (size_t)P * (sizeof(pe::TreeSel) / sizeof(uint32_t));
-      for (int64_t j = 0; j < n_jobs; ++j) {
-        const int64_t p = pof[(size_t)j];
-        const pe::TreeSel& r = a[p];
-        if (out_level) out_level[j] = r.level;
-        if (out_domain) out_domain[j] = r.domain;
-        if (out_domain_slots) out_domain_slots[j] = (int64_t)r.slots;
-        if (out_feasible)
-          for (int l = 0; l < n_levels; ++l) out_feasible[j * n_levels + l] = (int32_t)f[p * n_levels + l];
-      }
-    }
-    if (events)
-      ctx->err = "S=" + std::to_string(S) + " P=" + std::to_string(P) + " kernels_ms=" + std::to_string(kernel_ms);
     return PE_OK;
   });
 }

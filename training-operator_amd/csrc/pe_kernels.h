@@ -1,5 +1,5 @@
-// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp and pe_engine_greedy.cpp launches
-// these through the wrappers below; nothing here is part of the C ABI.
+// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp, pe_engine_greedy.cpp and
+// pe_engine_capacity.cpp launches these through the wrappers below; nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -466,29 +466,16 @@ static_assert(sizeof(CapAcc) == 16, "CapAcc must be 16 B");
 hipError_t launch_gang_capacity(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
                                 const CapShape* shapes, int64_t S, CapAcc* partials, CapAcc* out);
 
-// ---- gang capacity per topology domain (pe_gang_capacity_domains, pe_domains.hip)
+// ---- gang capacity per topology domain: the leaf table of both table calls (pe_domains.hip)
 constexpr int DM_MAX_DOMAINS = 65536;            // PE_MAX_DOMAINS
-// A distinct (shape, count) of a call that asks for a selection; its answer.
-struct DomPick {
-  uint32_t shape;   // index into the call's distinct shapes
-  int32_t count;    // >= 1
-};
-struct DomSel {
-  uint64_t slots;     // the chosen domain's slots, 0 when none
-  int32_t domain;     // smallest dom_slots >= count, ties to the smallest id; -1 when none
-  uint32_t feasible;  // domains with dom_slots >= count
-};
-static_assert(sizeof(DomPick) == 8 && sizeof(DomSel) == 16, "DomPick / DomSel layout");
 // dom_slots / dom_nodes [S][n_domains] += over the shard's Ns nodes (the caller zeroes them; dom_nodes may be
 // NULL: not computed), domain of node n = island[n].
 hipError_t launch_gang_capacity_domains(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
                                         const int32_t* island, int64_t Ns, const CapShape* shapes, int64_t S,
                                         int n_domains, uint64_t* dom_slots, uint32_t* dom_nodes);
-// out[p] for every pick p < P whose shape lies in [s0, s0 + S), from the rows dom_slots[shape - s0].
-hipError_t launch_domain_select(hipStream_t s, const uint64_t* dom_slots, int64_t s0, int64_t S, int n_domains,
-                                const DomPick* picks, int64_t P, DomSel* out);
 
-// ---- gang capacity over a topology hierarchy (pe_gang_capacity_tree, pe_tree.hip; the plan: pe_tree_plan.h)
+// ---- gang capacity over a topology hierarchy (pe_gang_capacity_tree, and pe_gang_capacity_domains as the
+// hierarchy of one level; pe_tree.hip; the plan: pe_tree_plan.h)
 constexpr int TR_MAX_LEVELS = 4;                 // PE_MAX_LEVELS
 // A distinct (shape, count, max_level) of a call that asks for a selection; its answer.
 struct TreePick {

@@ -1,7 +1,7 @@
-// Gang capacity over a topology hierarchy (pe_gang_capacity_tree): the leaf table of pe_domains.hip
-// ([shape][leaf domain] slots and nodes) rolled up along the caller's parent map, level by level, and the
-// selection that walks the levels.  The plan (pe_tree_plan.h) gives per upper level a CSR of child lists
-// and the lanes per parent.
+// Gang capacity over a topology hierarchy (pe_gang_capacity_tree, and pe_gang_capacity_domains as its
+// one-level case): the leaf table of pe_domains.hip ([shape][leaf domain] slots and nodes) rolled up along
+// the caller's parent map, level by level, and the selection that walks the levels.  The plan
+// (pe_tree_plan.h) gives per upper level a CSR of child lists and the lanes per parent.
 //
 // tree_rollup_kernel: one launch per upper level.  A group of w lanes (w a power of two <= 64, so a group
 // never leaves its wave) owns one (shape, parent): its lanes stride over the parent's child list, gather
@@ -15,27 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include "pe_kernels.h"
+#include "pe_wave.h"
 
 namespace pe {
 
 namespace {
 
 constexpr int TR_THREADS = 256;
-
-// Sum over each aligned group of w lanes (w a wave-uniform power of two), as pe_domains.hip folds.
-__device__ __forceinline__ uint64_t group_sum_u64(uint64_t v, int w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    if (o < w) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t group_sum_u32(uint32_t v, int w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    if (o < w) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(TR_THREADS) void tree_rollup_kernel(
     const unsigned long long* __restrict__ lo_slots, const uint32_t* __restrict__ lo_nodes, int64_t lo_pitch,

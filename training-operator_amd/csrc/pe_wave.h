@@ -1,9 +1,25 @@
-// Wave-level building blocks shared by the fit-mask kernels (device code only).
+// Wave-level building blocks shared by the fit-mask and the gang-capacity kernels (device code only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace pe {
+
+// Sum over each aligned group of w lanes (w a wave-uniform power of two, 64 at most): the capacity tables'
+// per-domain folds (pe_domains.hip) and the roll-up's per-parent folds (pe_tree.hip).
+__device__ __forceinline__ uint64_t group_sum_u64(uint64_t v, int w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    if (o < w) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t group_sum_u32(uint32_t v, int w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    if (o < w) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // Column sums of a 64 x 64 block: p[k] holds, per lane, a partial count of job k; returns F with
 // F[l] = sum over all 64 lanes of p[sigma(l)] for a fixed permutation sigma of 0..63 (find it by
