@@ -735,6 +735,23 @@ func (e *Engine) PlaceGreedy(g *Gangs) (podNode, jobStatus []int32, err error) {
 	return podNode, jobStatus, e.err(rc, "pe_place_greedy")
 }
 
+// PlaceGreedyDomains is PlaceGreedy with job j's pods confined to the nodes whose level-`level` domain is
+// jobDomain[j] ([J], each in [0, levelSize[level])): the call that acts on GangCapacityTree's answer.
+// levelSize and parent describe the hierarchy exactly as for GangCapacityTree (parent nil allowed with one
+// level); one call has one level.  Residuals are updated in place.  A sharded engine refuses the call.
+func (e *Engine) PlaceGreedyDomains(g *Gangs, jobDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, fmt.Errorf("PlaceGreedyDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	rc := C.pe_place_greedy_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), ptr32(jobDomain), C.int32_t(level), C.int32_t(len(levelSize)),
+		ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus))
+	return podNode, jobStatus, e.err(rc, "pe_place_greedy_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

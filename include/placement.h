@@ -446,6 +446,39 @@ int pe_place_greedy(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, c
                     const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need,
                     int32_t* out_pod_node, int32_t* out_job_status);
 
+/* (ABI 7, additive) Gang placement inside a chosen topology domain: the call that acts on
+ * pe_gang_capacity_tree's answer ("rack 1733 holds this gang" -> place the gang in rack 1733; Kueue's
+ * "required: rack").  NO reference function, as pe_place_greedy.  Levels, columns, level_size and parent
+ * mean exactly what they mean in pe_gang_capacity_tree (nothing of the hierarchy is kept in the context).
+ * The level-l domain of node n:
+ *   dom_0(n)     = island[n] if it lies in [0, level_size[0]), else none (a removed slot is in no domain)
+ *   dom_{l+1}(n) = parent[off_l + dom_l(n)], or none if that is -1 or dom_l(n) is none
+ * The rule is pe_place_greedy's with one more condition in fit: job j's pods land
+ * only on nodes with dom_level(n) == job_domain[j].  Everything else is unchanged: jobs in (priority desc,
+ * index asc) order, groups in the given order, each pod on the argmin-key node, all-or-nothing with
+ * rollback, PE_NEED_ISLAND groups as one unit of count x request on one node (a product that overflows
+ * fits nowhere), out_pod_node slots in group input order with GLOBAL node ids and -1 for none,
+ * out_job_status as before, residuals updated in place (successful placements stay).  Equivalently: per
+ * domain, pe_place_greedy on the sub-inventory of that domain's nodes with that domain's jobs.
+ * One call has one level; every job_domain[j] lies in [0, level_size[level]) (an unconstrained job belongs
+ * to pe_place_greedy).  A job whose domain has no node is PE_JOB_UNSCHEDULABLE, a job with no pods
+ * PE_JOB_PLACED; n_jobs == 0 is PE_OK.  Jobs of different domains touch disjoint nodes, so the device
+ * places all domains in parallel, one workgroup each, and the sequential rule binds only inside a domain.
+ * After the call the device residuals and the host mirror both hold the new residuals: a following
+ * pe_place_greedy, fit-mask run or capacity call sees them; pe_reset_residuals restores as usual and the
+ * staged fit batch stays valid.  pe_stats: adds to pods_placed, jobs_placed and jobs_failed only.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there
+ * is one): everything pe_place_greedy refuses (a negative request or count, bad offsets, a missing array),
+ * a NULL job_domain, a job_domain out of range, level outside [0, n_levels), and everything
+ * pe_gang_capacity_tree refuses about the hierarchy.  PE_ESTATE: a call before pe_load_nodes. */
+int pe_place_greedy_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                            const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                            const int32_t* job_domain /*[J]*/, int32_t level,
+                            int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                            const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                            int32_t* out_pod_node, int32_t* out_job_status);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

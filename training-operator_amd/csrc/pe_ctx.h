@@ -1,5 +1,5 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
+// pe_engine_capacity.cpp, pe_engine_place.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
 // the context itself.  Not part of the ABI.
 #pragma once
 
@@ -389,6 +389,17 @@ struct pe_ctx {
   HostBuf<uint32_t> lv_hout;
   std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
   std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
+  // gang placement inside a domain (pe_place_greedy_domains, pe_engine_place.cpp).  Every call sizes and fills
+  // what it uses, so calls of any shape may alternate with every other entry point; nothing of the hierarchy
+  // or the batch outlives a call.  Grow and are reused.
+  HostBuf<uint8_t> pl_hin;      // one copy in: G PlaceGroup, J PlaceJob, then leaf_dom, act_of and job_start
+  DevBuf<uint8_t> pl_in;
+  DevBuf<int32_t> pl_out;       // one copy out: out_pod_node [P], then out_job_status [J]
+  HostBuf<int32_t> pl_hout;
+  DevBuf<int32_t> pl_log;       // the jobs' rollback logs, [P][3]
+  DevBuf<int32_t> pl_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
+  DevBuf<int64_t> pl_seg;       // the segments' residuals [4][stride]
+  DevBuf<uint32_t> pl_segw;     // their global ids and labels, [2][stride]
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -462,6 +473,8 @@ struct pe_ctx {
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
     lv_leaf.release(); lv_upper.release(); lv_hslots.release(); lv_hnodes.release();
     lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release();
+    pl_hin.release(); pl_in.release(); pl_out.release(); pl_hout.release(); pl_log.release(); pl_dom.release();
+    pl_seg.release(); pl_segw.release();
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -535,6 +548,39 @@ int guarded(pe_ctx* ctx, F&& body) {
 inline void need_ptr(const void* p, const char* name) {
   if (!p) raise(PE_EINVAL, std::string(name) + " is NULL");
 }
+
+// PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity*_latency.py, tools/place_domains_latency.py): hipEvents on
+// the context's stream around a call's kernels; a successful call then leaves "S=<shapes> [P=<picks>]
+// kernels_ms=<time>" (the capacity calls) or "A=<active domains> kernels_ms=<time>" (pe_place_greedy_domains) in
+// pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
+// it on and off inside one process.
+struct CapEvents {
+  pe_ctx* ctx;
+  const bool on;
+  bool recorded = false;
+  explicit CapEvents(pe_ctx* c) : ctx(c), on(std::getenv("PE_CAP_EVENTS") != nullptr) {}
+  void begin() {
+    if (!on) return;
+    for (hipEvent_t& e : ctx->cp_ev)
+      if (!e) hipchk(hipEventCreate(&e), "event create");
+    hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
+  }
+  void end() {
+    if (!on) return;
+    hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
+    recorded = true;
+  }
+  // after the stream was synchronised; P < 0: the call has no picks; no kernels ran: 0 ms
+  void report(int64_t S, int64_t P = -1) {
+    report_as("S=" + std::to_string(S) + (P < 0 ? "" : " P=" + std::to_string(P)));
+  }
+  void report_as(const std::string& what) {
+    if (!on) return;
+    float ms = 0.f;
+    if (recorded) hipchk(hipEventElapsedTime(&ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
+    ctx->err = what + " kernels_ms=" + std::to_string(ms);
+  }
+};
 
 // pe_engine.cpp's planning pool: f(0) on the caller, f(1 .. n-1) on pool threads; returns when all are
 // done, rethrows the first exception.

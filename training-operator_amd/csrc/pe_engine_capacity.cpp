@@ -80,35 +80,6 @@ int64_t cap_stage_shapes(pe_ctx* ctx) {
   return (int64_t)S;
 }
 
-// PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity*_latency.py): hipEvents on the context's stream around
-// a call's kernels; a successful call then leaves "S=<shapes> [P=<picks>] kernels_ms=<time>" in
-// pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
-// it on and off inside one process.
-struct CapEvents {
-  pe_ctx* ctx;
-  const bool on;
-  bool recorded = false;
-  explicit CapEvents(pe_ctx* c) : ctx(c), on(std::getenv("PE_CAP_EVENTS") != nullptr) {}
-  void begin() {
-    if (!on) return;
-    for (hipEvent_t& e : ctx->cp_ev)
-      if (!e) hipchk(hipEventCreate(&e), "event create");
-    hipchk(hipEventRecord(ctx->cp_ev[0], ctx->stream), "event record");
-  }
-  void end() {
-    if (!on) return;
-    hipchk(hipEventRecord(ctx->cp_ev[1], ctx->stream), "event record");
-    recorded = true;
-  }
-  // after the stream was synchronised; P < 0: the call has no picks; no kernels ran: 0 ms
-  void report(int64_t S, int64_t P = -1) {
-    if (!on) return;
-    float ms = 0.f;
-    if (recorded) hipchk(hipEventElapsedTime(&ms, ctx->cp_ev[0], ctx->cp_ev[1]), "event elapsed");
-    ctx->err = "S=" + std::to_string(S) + (P < 0 ? "" : " P=" + std::to_string(P)) + " kernels_ms=" + std::to_string(ms);
-  }
-};
-
 // The outputs of a table call over `plan`'s levels (T columns in all), each optional.
 struct LevelOut {
   int64_t* slots;          // [J][T]

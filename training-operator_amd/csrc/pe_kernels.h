@@ -1,5 +1,6 @@
-// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp, pe_engine_greedy.cpp and
-// pe_engine_capacity.cpp launches these through the wrappers below; nothing here is part of the C ABI.
+// Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp, pe_engine_greedy.cpp,
+// pe_engine_capacity.cpp and pe_engine_place.cpp launches these through the wrappers below; nothing here is part
+// of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -511,5 +512,50 @@ hipError_t launch_tree_rollup(hipStream_t s, const uint64_t* lo_slots, const uin
 hipError_t launch_tree_select(hipStream_t s, const uint64_t* leaf_slots, const uint64_t* upper_slots, int64_t s0,
                               int64_t S, const TreeLevels& levels, const TreePick* picks, int64_t P, TreeSel* out,
                               uint32_t* feasible);
+
+// ---- gang placement inside a chosen domain (pe_place_greedy_domains, pe_place.hip; the plan: pe_place_plan.h)
+constexpr int PL_THREADS = 256;       // threads of a domain's workgroup
+// A domain's working state (four residuals, labels, node id: 40 B per node) lives in LDS up to this many
+// nodes and in the compact global segment beyond.  1016 nodes are 40 640 B; with the 128 B of the waves' minima
+// a workgroup stays within 40 KiB, so four workgroups of four waves share a CU's 160 KiB (1024 nodes would
+// leave room for three).  A rack fits, a zone does not.
+constexpr int PL_LDS_NODES = 1016;
+// One group of the batch: request, need and count, and its first pod slot.
+struct alignas(64) PlaceGroup {
+  int64_t q[D];
+  uint32_t need;
+  int32_t count;
+  int64_t pod0;
+  uint32_t pad_[4];
+};
+static_assert(sizeof(PlaceGroup) == 64, "PlaceGroup must be 64 B");
+// One job, in plan order: its index in the caller's batch and its groups [g0, g1).
+struct PlaceJob {
+  int32_t job, g0, g1, pad_;
+};
+static_assert(sizeof(PlaceJob) == 16, "PlaceJob must be 16 B");
+// The per-domain member lists of one call.  The caller zeroes cnt[A]; after the launch seg_off[A + 1] holds the
+// active domains' segment bounds and segment a's places [seg_off[a], seg_off[a + 1]) its nodes' state: global
+// id, labels (lab = gid + seg_stride) and the four residuals ([D][seg_stride]), in any order.  leaf_dom[n_leaf] / act_of: the plan's
+// maps; a node whose island id lies outside [0, n_leaf), whose leaf has no domain or whose domain is inactive
+// is in no list.  cursor[A]: scratch.
+struct PlaceSegs {
+  int32_t* cnt;
+  int32_t* seg_off;
+  int32_t* cursor;
+  uint32_t* gid;
+  uint32_t* lab;
+  int64_t* res;
+  int64_t seg_stride;
+};
+hipError_t launch_place_members(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
+                                const int32_t* island, int64_t Ns, uint64_t id_base, const int32_t* leaf_dom,
+                                int n_leaf, const int32_t* act_of, int A, const PlaceSegs& segs);
+// One workgroup per active domain a < A: its jobs jobs[job_start[a] .. job_start[a + 1]) in that order, placed
+// on its segment by the Appendix-B rule.  out_pod [P] (every slot of a job with pods is written), out_status by
+// the caller's job index, log: 3 int32 of scratch per pod slot; at the end the segment's residuals go back to res.
+hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* job_start,
+                                int A, const PlaceSegs& segs, int64_t* res, int64_t stride, uint64_t id_base,
+                                int32_t* out_pod, int32_t* out_status, int32_t* log);
 
 }  // namespace pe

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "pe_kernels.h"
+#include "pe_node_key.h"
 #include "pe_wave.h"
 
 namespace pe {
@@ -1258,21 +1259,7 @@ hipError_t launch_fit_mask_planes(hipStream_t s, const uint32_t* planes, int64_t
 
 // ------------------------------------------------------------------ best-fit scan (configs 2-4)
 
-// Appendix B key: fit ? (score << 24) | gid : NO_KEY, score = min(a+b+c+d, 2^40-1) with
-// a = left_cpu, b = left_mem >> 20, c = left_gpu << 20, d = left_eph >> 24, each term saturated.
-__device__ __forceinline__ uint64_t node_key(int64_t r0, int64_t r1, int64_t r2, int64_t r3, uint32_t lab,
-                                             int64_t q0, int64_t q1, int64_t q2, int64_t q3, uint32_t need,
-                                             uint64_t gid) {
-  const bool fit = ((lab & need) == need) & (q0 <= r0) & (q1 <= r1) & (q2 <= r2) & (q3 <= r3);
-  const uint64_t a = (uint64_t)r0 - (uint64_t)q0;
-  const uint64_t b = ((uint64_t)r1 - (uint64_t)q1) >> 20;
-  const uint64_t c = (uint64_t)r2 - (uint64_t)q2;
-  const uint64_t d = ((uint64_t)r3 - (uint64_t)q3) >> 24;
-  const bool big = (a > SCORE_MAX) | (b > SCORE_MAX) | (c >= (1ull << 20)) | (d > SCORE_MAX);
-  const uint64_t sum = a + b + (c << 20) + d;      // < 2^42 whenever !big
-  const uint64_t score = (big | (sum > SCORE_MAX)) ? SCORE_MAX : sum;
-  return fit ? ((score << 24) | gid) : NO_KEY;
-}
+// (the Appendix B key itself, node_key: pe_node_key.h, shared with pe_place.hip)
 
 // Node-only part of the Appendix-B score, kept per node for the scan:
 //   S(n) = r0 + (r1 >> 20) + (r2 << 20) + (r3 >> 24),   K(n) = (S << 24) | gid.

@@ -1,0 +1,348 @@
+// Gang placement inside a chosen topology domain (pe_place_greedy_domains).  Jobs pinned to different
+// domains touch disjoint nodes, so the sequential greedy rule binds only inside a
+// domain: one workgroup per ACTIVE domain (a domain with at least one job) runs its jobs' decisions on the
+// device, all domains in parallel -- no host resolver, no windows, no candidate lists.
+//
+// Member lists (place_count_kernel, place_scan_kernel, place_fill_kernel): every node's level-`level` domain
+// through the plan's leaf_dom, its active index through act_of; the nodes are counted per active domain, the
+// counts scanned into segment bounds, and each node's state (global id, labels, four residuals) is gathered
+// into its domain's segment, so the placement reads contiguous memory.  A node's place inside its segment
+// comes from an atomic cursor and differs from run to run; every key carries the node id (unique, low 24
+// bits), so no result depends on that order.  A domain without nodes has a zero-length segment and still
+// gets its workgroup, which fails the jobs that have pods and passes the others.
+//
+// place_domains_kernel: the workgroup walks its jobs in plan order, group by group.  Per decision every
+// thread scores its share of the segment with node_key (pe_node_key.h) against the working residuals and
+// finds what its own best node would take; a wave butterfly (pe_wave.h) and one cross-wave step through LDS
+// give the block's minimum key with that node's place and take.  The chosen node takes
+//   t = min(pods left, min over d with q_d > 0 of floor(res_d / q_d))      (no q_d > 0: all the pods left)
+// pods at once -- exact: a node's key never rises as its leftover falls, so it stays the minimum while it
+// fits (the host resolver does the same), and counts reach 2^31 - 1, so one pod per
+// decision is not an option.  An island group is one decision for count x request.  Thread i mod PL_THREADS
+// is the only one that reads or writes place i of the working state outside a rollback, so a decision costs
+// one barrier.  A job that cannot place a pod gives back what it took from its log of (place, group, pods)
+// entries -- kept in the job's own pod range of the scratch array: every entry places at least one pod --
+// and its pod slots become -1.  The working state lives in LDS for segments up to PL_LDS_NODES nodes and in
+// the global segment beyond (two instances of the kernel, each taking its kind of segment); at the end the
+// workgroup writes its nodes' residuals back to the live SoA.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "pe_kernels.h"
+#include "pe_node_key.h"
+#include "pe_wave.h"
+
+namespace pe {
+
+namespace {
+
+constexpr int PM_THREADS = 256;
+constexpr int PL_WAVES = PL_THREADS / 64;
+constexpr uint32_t NEED_ISLAND = 0x80000000u;   // PE_NEED_ISLAND
+
+// The active index of local node n, -1 for none.
+__device__ __forceinline__ int node_active(const int32_t* __restrict__ island, int64_t n,
+                                           const int32_t* __restrict__ leaf_dom, int n_leaf,
+                                           const int32_t* __restrict__ act_of) {
+  const int32_t isl = island[n];
+  if ((uint32_t)isl >= (uint32_t)n_leaf) return -1;
+  const int32_t d = leaf_dom[isl];   // < the level's size: the plan validated the map
+  return d < 0 ? -1 : act_of[d];
+}
+
+// ctr[a] += 1 for every lane with a >= 0; returns the lane's value before (unspecified for a < 0).  A wave
+// whose lanes all name one domain -- contiguous racks -- issues one atomic instead of 64.  Called by whole waves.
+__device__ __forceinline__ int32_t wave_take(int a, int32_t* ctr, int lane) {
+  const int first = __builtin_amdgcn_readfirstlane(a);
+  if (__all(a == first)) {
+    if (first < 0) return 0;
+    int32_t base = 0;
+    if (lane == 0) base = atomicAdd(&ctr[first], 64);
+    return __builtin_amdgcn_readfirstlane(base) + lane;
+  }
+  return a >= 0 ? atomicAdd(&ctr[a], 1) : 0;
+}
+
+__global__ __launch_bounds__(PM_THREADS) void place_count_kernel(const int32_t* __restrict__ island, int64_t Ns,
+                                                                 const int32_t* __restrict__ leaf_dom, int n_leaf,
+                                                                 const int32_t* __restrict__ act_of,
+                                                                 int32_t* __restrict__ cnt) {
+  const int64_t n = (int64_t)blockIdx.x * PM_THREADS + threadIdx.x;
+  const int a = n < Ns ? node_active(island, n, leaf_dom, n_leaf, act_of) : -1;
+  (void)wave_take(a, cnt, threadIdx.x & 63);
+}
+
+// seg_off[0 .. A] = exclusive scan of cnt[0 .. A), cursor[a] = seg_off[a].  One block: A <= 65536.
+__global__ __launch_bounds__(1024) void place_scan_kernel(const int32_t* __restrict__ cnt, int A,
+                                                          int32_t* __restrict__ seg_off, int32_t* __restrict__ cursor) {
+  __shared__ int32_t part[1024];
+  const int tid = threadIdx.x;
+  const int per = (A + 1023) / 1024;
+  const int lo = min(tid * per, A), hi = min(lo + per, A);
+  int32_t sum = 0;
+  for (int i = lo; i < hi; ++i) sum += cnt[i];
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    int32_t run = 0;
+    for (int i = 0; i < 1024; ++i) {
+      const int32_t v = part[i];
+      part[i] = run;
+      run += v;
+    }
+    seg_off[A] = run;
+  }
+  __syncthreads();
+  int32_t run = part[tid];
+  for (int i = lo; i < hi; ++i) {
+    seg_off[i] = run;
+    cursor[i] = run;
+    run += cnt[i];
+  }
+}
+
+__global__ __launch_bounds__(PM_THREADS) void place_fill_kernel(
+    const int64_t* __restrict__ res, int64_t stride, const uint32_t* __restrict__ labels,
+    const int32_t* __restrict__ island, int64_t Ns, uint32_t id_base, const int32_t* __restrict__ leaf_dom, int n_leaf,
+    const int32_t* __restrict__ act_of, PlaceSegs sg) {
+  const int64_t n = (int64_t)blockIdx.x * PM_THREADS + threadIdx.x;
+  const int a = n < Ns ? node_active(island, n, leaf_dom, n_leaf, act_of) : -1;
+  const int32_t at = wave_take(a, sg.cursor, threadIdx.x & 63);   // < seg_off[a + 1] <= Ns: the count pass saw the same nodes
+  if (a < 0) return;
+  sg.gid[at] = id_base + (uint32_t)n;
+  sg.lab[at] = labels[n];
+#pragma unroll
+  for (int d = 0; d < D; ++d) sg.res[d * sg.seg_stride + at] = res[d * stride + n];
+}
+
+// What node state (r0 .. r3) takes of `left` pods of request q: min(left, min over q_d > 0 of floor(r_d / q_d)).
+// Called for a node that fits one pod, so every r_d >= q_d >= 0.
+__device__ __forceinline__ uint32_t take_of(int64_t r0, int64_t r1, int64_t r2, int64_t r3, int64_t q0, int64_t q1,
+                                            int64_t q2, int64_t q3, uint32_t left) {
+  uint64_t t = left;
+  if (q0 > 0) t = min(t, (uint64_t)r0 / (uint64_t)q0);
+  if (q1 > 0) t = min(t, (uint64_t)r1 / (uint64_t)q1);
+  if (q2 > 0) t = min(t, (uint64_t)r2 / (uint64_t)q2);
+  if (q3 > 0) t = min(t, (uint64_t)r3 / (uint64_t)q3);
+  return (uint32_t)t;
+}
+
+struct PlaceShared {   // the global segment's shape with a stride of PL_LDS_NODES
+  int64_t r[D][PL_LDS_NODES];
+  uint32_t gid[PL_LDS_NODES];
+  uint32_t lab[PL_LDS_NODES];
+};
+struct PlaceMin {   // the waves' minima of a decision, two sets used in turn: one barrier per decision
+  uint64_t key[2][PL_WAVES];
+  uint32_t at[2][PL_WAVES];
+  uint32_t take[2][PL_WAVES];
+};
+
+// A failed job gives back what it took: its n_log log entries (place, group, pods) added back to the working
+// state r[d * rs + place] and its n_pods pod slots set to -1.  Out of line, on generic pointers (the state is in
+// LDS or global memory): the path is cold, and inlined its uniform values cost the decision loop SGPRs.
+__device__ __noinline__ void place_rollback(int64_t* r, int64_t rs, const PlaceGroup* __restrict__ groups,
+                                            const int32_t* __restrict__ entries, int64_t n_log, int32_t* __restrict__ pods,
+                                            int64_t n_pods) {
+  const int tid = threadIdx.x;
+  for (int64_t e = tid; e < n_log; e += PL_THREADS) {
+    const int32_t* const en = entries + 3 * e;
+    const int64_t t = en[2];
+    const PlaceGroup& gr = groups[en[1]];
+    int64_t* const at = r + en[0];   // a place of the segment: the decision wrote it
+#pragma unroll
+    for (int d = 0; d < D; ++d)   // two entries may name one node: atomic
+      atomicAdd((unsigned long long*)(at + d * rs), (unsigned long long)(t * gr.q[d]));
+  }
+  for (int64_t p = tid; p < n_pods; p += PL_THREADS) pods[p] = -1;
+}
+
+// One domain's jobs on its n nodes, whose working state is r[d * rs + i] (written), gid[i] and labels gid[rs + i].
+template <class Stride>
+__device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, Stride rs, int n, PlaceMin& mn,
+                                             const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs,
+                                             int j0, int j1, int32_t* __restrict__ out_pod,
+                                             int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t* const r1 = r0 + rs;
+  int64_t* const r2 = r1 + rs;
+  int64_t* const r3 = r2 + rs;
+  const uint32_t* const lab = gid + rs;
+  // log entry e, three words at log[3 e]: its place in the segment, its group, the pods it placed
+  int par = 0;
+  for (int ji = j0; ji < j1; ++ji) {
+    const int g0 = jobs[ji].g0, g1 = jobs[ji].g1;
+    if (g0 == g1) {   // no groups: placed
+      if (tid == 0) out_status[jobs[ji].job] = 0;
+      continue;
+    }
+    const int64_t pod0 = groups[g0].pod0;   // the job's pod slots: [pod0, the last group's pod0 + count)
+    int64_t n_log = 0;   // entries of this job, at log[pod0 ..]; <= the pods it placed
+    bool ok = true;
+    for (int g = g0; g < g1 && ok; ++g) {
+      const PlaceGroup gr = groups[g];
+      if (gr.count <= 0) continue;
+      const bool unit = (gr.need & NEED_ISLAND) != 0;   // an island group: one decision for count x request
+      int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];   // the request the scan scores
+      if (unit) {
+        bool ovf = __builtin_mul_overflow(gr.q[0], (int64_t)gr.count, &s0);
+        ovf |= __builtin_mul_overflow(gr.q[1], (int64_t)gr.count, &s1);
+        ovf |= __builtin_mul_overflow(gr.q[2], (int64_t)gr.count, &s2);
+        ovf |= __builtin_mul_overflow(gr.q[3], (int64_t)gr.count, &s3);
+        if (ovf) {   // fits nowhere
+          ok = false;
+          break;
+        }
+      }
+      uint32_t left = (uint32_t)gr.count;
+      int64_t slot = gr.pod0;
+      while (left > 0) {
+        uint64_t bk = NO_KEY;
+        uint32_t bi = 0, bt = 0;
+        for (int i = tid; i < n; i += PL_THREADS) {
+          const uint64_t k = node_key(r0[i], r1[i], r2[i], r3[i], lab[i], s0, s1, s2, s3, gr.need, gid[i]);
+          if (k < bk) {
+            bk = k;
+            bi = (uint32_t)i;
+          }
+        }
+        if (bk != NO_KEY) bt = unit ? left : take_of(r0[bi], r1[bi], r2[bi], r3[bi], s0, s1, s2, s3, left);
+        wave_argmin_u64(bk, bi, bt);
+        if (lane == 0) {
+          mn.key[par][wave] = bk;
+          mn.at[par][wave] = bi;
+          mn.take[par][wave] = bt;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < PL_WAVES; ++w) {
+          const uint64_t k = mn.key[par][w];
+          if (w == 0 || k < bk) {
+            bk = k;
+            bi = mn.at[par][w];
+            bt = mn.take[par][w];
+          }
+        }
+        par ^= 1;
+        // the same on every thread; said so for the branches and barriers that follow
+        const uint32_t klo = __builtin_amdgcn_readfirstlane((uint32_t)bk);
+        const uint32_t khi = __builtin_amdgcn_readfirstlane((uint32_t)(bk >> 32));
+        const uint32_t at = __builtin_amdgcn_readfirstlane(bi), t = __builtin_amdgcn_readfirstlane(bt);
+        if ((klo & khi) == 0xFFFFFFFFu) {   // NO_KEY: no node of the domain fits
+          ok = false;
+          break;
+        }
+        if ((at & (PL_THREADS - 1)) == (uint32_t)tid) {   // the place's owner; m * s_d <= r_d
+          const int64_t m = unit ? 1 : (int64_t)t;           // (unit: s = count x request, t = count)
+          r0[at] -= m * s0;
+          r1[at] -= m * s1;
+          r2[at] -= m * s2;
+          r3[at] -= m * s3;
+        }
+        if (tid == 0) {   // n_log < the pods the job placed so far, this decision's included
+          int32_t* const e = log + 3 * (pod0 + n_log);
+          e[0] = (int32_t)at;
+          e[1] = g;
+          e[2] = (int32_t)t;
+        }
+        ++n_log;
+        const int32_t node = (int32_t)(klo & 0xFFFFFFu);
+        for (int64_t p = slot + tid; p < slot + t; p += PL_THREADS) out_pod[p] = node;   // slot + t <= pod1 <= P
+        slot += t;
+        left -= t;
+      }
+    }
+    if (!ok) {
+      // every update and pod store of this job lies before the barrier of the decision that failed -- or,
+      // for an overflowing island group, before this one
+      __syncthreads();
+      place_rollback(r0, (int64_t)rs, groups, log + 3 * pod0, n_log, out_pod + pod0,
+                     groups[g1 - 1].pod0 + groups[g1 - 1].count - pod0);
+      __syncthreads();   // the owners read their places again
+    }
+    if (tid == 0) out_status[jobs[ji].job] = ok ? 0 : 1;
+  }
+}
+
+// IN_LDS: the instance for the segments of at most PL_LDS_NODES nodes, whose working state it stages in LDS;
+// the other instance takes the larger segments and works on the global segment in place.  Both are launched
+// over all the active domains and a workgroup whose segment is the other instance's leaves at once (one
+// kernel with both paths held more uniform values than there are SGPRs).
+template <bool IN_LDS>
+__global__ __launch_bounds__(PL_THREADS) void place_domains_kernel(
+    const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs, const int32_t* __restrict__ job_start,
+    PlaceSegs sg, int64_t* __restrict__ res, int64_t stride, uint32_t id_base, int32_t* __restrict__ out_pod,
+    int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
+  __shared__ PlaceMin mn;
+  const int a = blockIdx.x, tid = threadIdx.x;
+  const int b = sg.seg_off[a], n = sg.seg_off[a + 1] - b;
+  if ((n <= PL_LDS_NODES) != IN_LDS) return;
+  const int j0 = job_start[a], j1 = job_start[a + 1];
+  int64_t* const g0 = sg.res + b;
+  const int64_t ss = sg.seg_stride;
+  int64_t* const g1 = g0 + ss;
+  int64_t* const g2 = g1 + ss;
+  int64_t* const g3 = g2 + ss;
+  const uint32_t* const gid = sg.gid + b;
+  if constexpr (IN_LDS) {
+    __shared__ PlaceShared sh;
+    for (int i = tid; i < n; i += PL_THREADS) {   // thread i mod PL_THREADS owns place i: no barrier
+      sh.r[0][i] = g0[i];
+      sh.r[1][i] = g1[i];
+      sh.r[2][i] = g2[i];
+      sh.r[3][i] = g3[i];
+      sh.lab[i] = gid[ss + i];
+      sh.gid[i] = gid[i];
+    }
+    place_domain(sh.r[0], sh.gid, std::integral_constant<int, PL_LDS_NODES>(), n, mn, groups, jobs, j0, j1, out_pod,
+                 out_status, log);
+    for (int i = tid; i < n; i += PL_THREADS) {
+      const int64_t l = (int64_t)(sh.gid[i] - id_base);   // < Ns: the fill kernel wrote id_base + local
+      res[l] = sh.r[0][i];
+      res[stride + l] = sh.r[1][i];
+      res[2 * stride + l] = sh.r[2][i];
+      res[3 * stride + l] = sh.r[3][i];
+    }
+  } else {
+    place_domain(g0, gid, ss, n, mn, groups, jobs, j0, j1, out_pod, out_status, log);
+    for (int i = tid; i < n; i += PL_THREADS) {
+      const int64_t l = (int64_t)(gid[i] - id_base);
+      res[l] = g0[i];
+      res[stride + l] = g1[i];
+      res[2 * stride + l] = g2[i];
+      res[3 * stride + l] = g3[i];
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_place_members(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
+                                const int32_t* island, int64_t Ns, uint64_t id_base, const int32_t* leaf_dom,
+                                int n_leaf, const int32_t* act_of, int A, const PlaceSegs& segs) {
+  if (A <= 0 || A > DM_MAX_DOMAINS || Ns < 0 || Ns > (int64_t(1) << 24)) return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((Ns + PM_THREADS - 1) / PM_THREADS);
+  if (blocks > 0)
+    hipLaunchKernelGGL(place_count_kernel, dim3(blocks), dim3(PM_THREADS), 0, s, island, Ns, leaf_dom, n_leaf, act_of,
+                       segs.cnt);
+  hipLaunchKernelGGL(place_scan_kernel, dim3(1), dim3(1024), 0, s, (const int32_t*)segs.cnt, A, segs.seg_off,
+                     segs.cursor);
+  if (blocks > 0)
+    hipLaunchKernelGGL(place_fill_kernel, dim3(blocks), dim3(PM_THREADS), 0, s, res, stride, labels, island, Ns,
+                       (uint32_t)id_base, leaf_dom, n_leaf, act_of, segs);
+  return hipGetLastError();
+}
+
+hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* job_start,
+                                int A, const PlaceSegs& segs, int64_t* res, int64_t stride, uint64_t id_base,
+                                int32_t* out_pod, int32_t* out_status, int32_t* log) {
+  if (A <= 0) return hipSuccess;
+  hipLaunchKernelGGL(place_domains_kernel<true>, dim3((unsigned)A), dim3(PL_THREADS), 0, s, groups, jobs, job_start, segs,
+                     res, stride, (uint32_t)id_base, out_pod, out_status, log);
+  hipLaunchKernelGGL(place_domains_kernel<false>, dim3((unsigned)A), dim3(PL_THREADS), 0, s, groups, jobs, job_start, segs,
+                     res, stride, (uint32_t)id_base, out_pod, out_status, log);
+  return hipGetLastError();
+}
+
+}  // namespace pe

@@ -21,6 +21,22 @@ __device__ __forceinline__ uint32_t group_sum_u32(uint32_t v, int w) {
   return v;
 }
 
+// The wave's smallest key with the two values its lane carried, on every lane (a six-step butterfly).  Keys
+// that carry a node id are unique, so no tie needs a rule; NO_KEY everywhere gives NO_KEY.  The domain
+// placement's per-decision argmin (pe_place.hip).
+__device__ __forceinline__ void wave_argmin_u64(uint64_t& key, uint32_t& a, uint32_t& b) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t ok = __shfl_xor(key, o, 64);
+    const uint32_t oa = __shfl_xor(a, o, 64), ob = __shfl_xor(b, o, 64);
+    if (ok < key) {
+      key = ok;
+      a = oa;
+      b = ob;
+    }
+  }
+}
+
 // Column sums of a 64 x 64 block: p[k] holds, per lane, a partial count of job k; returns F with
 // F[l] = sum over all 64 lanes of p[sigma(l)] for a fixed permutation sigma of 0..63 (find it by
 // reducing a probe, p[k] = (lane == 0) ? k : 0).  Six halving levels, each pairing two registers

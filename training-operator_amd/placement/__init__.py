@@ -537,6 +537,32 @@ class Engine:
         return self.place_greedy(batch.job_group_off, batch.priority, batch.group_count, batch.group_req,
                                  batch.group_need)
 
+    def place_greedy_domains(self, job_group_off, priority, group_count, group_req, group_need, job_domain, level,
+                             level_size, parent=None):
+        """pe_place_greedy_domains: place_greedy with job j's pods confined to the nodes whose level-`level`
+        domain is job_domain[j] ([J], each in [0, level_size[level])).  level_size / parent describe the hierarchy
+        exactly as for gang_capacity_tree (parent None allowed with one level); one call has one level.
+        Residuals are updated in place.  Returns (pod_node, job_status) like place_greedy."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        dom = None if job_domain is None else _c(job_domain, np.int32)
+        if dom is not None and dom.shape != (J,):
+            raise ValueError("job_domain must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        self._chk(self.lib.pe_place_greedy_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
+                                                   _p(nd), _p(dom), int(level), len(ls), _p(ls), _p(par), _p(pod),
+                                                   _p(st)), "pe_place_greedy_domains")
+        return pod[:P], st[:J]
+
     # ------------------------------------------------------------ misc
     def synchronize(self):
         self._chk(self.lib.pe_synchronize(self.h), "pe_synchronize")

@@ -91,6 +91,7 @@ SIGNATURES = {
     "pe_fit_mask_layout": (ctypes.c_int, [P, ctypes.POINTER(i32)]),
     "pe_fit_mask_row_pitch": (ctypes.c_int, [P, ctypes.POINTER(i64)]),
     "pe_place_greedy": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P]),
+    "pe_place_greedy_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
