@@ -752,6 +752,30 @@ func (e *Engine) PlaceGreedyDomains(g *Gangs, jobDomain []int32, level int32, le
 	return podNode, jobStatus, e.err(rc, "pe_place_greedy_domains")
 }
 
+// GangFitDomains answers, for every pair p, whether PlaceGreedyDomains would place job pairJob[p] ALONE in the
+// level-`level` domain pairDomain[p] against the current residuals (Gangs.Priority is not read).  Read-only.
+// fits[p] is 1 or 0, failGroup[p] -1 or the job's first group that was not placed in full, pods[p] the pods
+// placed when the rule stopped, first[j] the smallest fitting pair of job j or -1: first fit in the caller's
+// pair order.  selectionOnly leaves the three per-pair answers nil (they never cross).  levelSize and parent
+// describe the hierarchy exactly as for GangCapacityTree.  A sharded engine refuses the call.
+func (e *Engine) GangFitDomains(g *Gangs, pairJob, pairDomain []int32, level int32, levelSize, parent []int32, selectionOnly bool) (fits []uint8, failGroup []int32, pods []int64, first []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	P := len(pairJob)
+	if len(pairDomain) != P {
+		return nil, nil, nil, nil, fmt.Errorf("GangFitDomains: %d jobs for %d domains", P, len(pairDomain))
+	}
+	first = make([]int32, J)
+	if !selectionOnly {
+		fits = make([]uint8, P)
+		failGroup = make([]int32, P)
+		pods = make([]int64, P)
+	}
+	rc := C.pe_gang_fit_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.GroupCount), ptr64(g.GroupReq),
+		ptru32(g.GroupNeed), C.int64_t(P), ptr32(pairJob), ptr32(pairDomain), C.int32_t(level), C.int32_t(len(levelSize)),
+		ptr32(levelSize), ptr32(parent), ptr8(fits), ptr32(failGroup), ptr64(pods), ptr32(first))
+	return fits, failGroup, pods, first, e.err(rc, "pe_gang_fit_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

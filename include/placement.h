@@ -335,7 +335,8 @@ int pe_fit_mask_row_pitch(const pe_ctx* ctx, int64_t* words);
  * Exact: integer division of the int64 residuals, no rounding.  Per shard, as pe_fit_mask's counts:
  * the caller adds out_slots and out_nodes over shards and takes the maximum of out_max_node.  A job
  * of several groups needs every group's capacity, which is necessary, not sufficient: its exact
- * answer is pe_place_greedy.  Residuals and the staged fit-mask state (pe_jobs_upload ...
+ * read-only answer within a domain is pe_gang_fit_domains (against the whole shard: pe_place_greedy,
+ * which places it).  Residuals and the staged fit-mask state (pe_jobs_upload ...
  * pe_fit_mask_rows) are left as they are.  Each out_* may be NULL; need NULL = 0.  A negative request
  * is PE_EINVAL (the first offending index in pe_last_error), a call before pe_load_nodes PE_ESTATE. */
 #define PE_CAP_MAX 2147483647 /* per-node capacity saturates here: the largest group_count */
@@ -478,6 +479,56 @@ int pe_place_greedy_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                             int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
                             const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                             int32_t* out_pod_node, int32_t* out_job_status);
+
+/* (ABI 7, additive) Exact what-if of a whole gang per domain: would this job, all its groups in order, be
+ * placed in this domain right now?  The read-only link between pe_gang_capacity_tree (which domains hold a
+ * gang of ONE shape) and pe_place_greedy_domains (which places the gang and changes the residuals).  For a
+ * job of several groups -- a PyTorchJob's Master and Workers, an MPIJob's launcher and workers -- every
+ * capacity call can say yes for a domain in which the placement then fails.  The smallest case: a rack of
+ * two nodes with 8 free GPUs each, group A = 2 pods x 5 GPUs followed by group B = 3 pods x 2 GPUs.
+ * MinResources is 16 <= 16 free, A's slots are 2 >= 2, B's slots are 8 >= 3; but once A has taken one node
+ * each, 3 + 3 GPUs are left and B places two of its three pods.  This call answers 0, fail_group 1, pods 4.
+ * NO reference function, as pe_place_greedy_domains.  Levels, columns, level_size, parent and dom_level(n)
+ * mean exactly what they mean in pe_place_greedy_domains; nothing of the hierarchy is kept in the context;
+ * one call has one level.
+ * Pair p asks: against the CURRENT residuals of the context, with no other job in the call, would
+ * pe_place_greedy_domains given the single job pair_job[p] with job_domain = pair_domain[p] return
+ * PE_JOB_PLACED?  The rule is that call's, unchanged: groups in the given order, each pod on the argmin-key
+ * node of the domain, PE_NEED_ISLAND groups as one unit of count x request on one node (a product that
+ * overflows fits nowhere), zero-count groups skipped, a job without groups or pods is placed, a domain
+ * without nodes holds only a job with no pod to place.  There is no priority: every pair is judged alone.
+ *   out_fits[p]       = 1 or 0
+ *   out_fail_group[p] = -1 when the pair fits, else the index within the job (0 = its first group) of the
+ *                       first group that could not be placed in full
+ *   out_pods[p]       = the pods the rule had placed when it stopped: the job's pod total when the pair fits,
+ *                       else the pods of the earlier groups plus the pods of the failing group placed before
+ *                       the first pod that found no node (a failing island group contributes 0)
+ *   out_first[j]      = the smallest p with pair_job[p] == j and out_fits[p] == 1, -1 when there is none:
+ *                       first fit in the CALLER's order, who expresses preference by ordering the pairs
+ *                       (pe_gang_capacity_tree's slots, lowest level first over several calls, ...)
+ * out_first is computed on the device; a caller who wants only the selection passes the three P-sized
+ * outputs NULL and they never cross.  Each out_* may be NULL; group_need NULL = 0.
+ * The pairs may come in any order, need not be grouped by job, may repeat and may name any number of
+ * domains; a job in no pair has out_first -1.  n_pairs == 0 and n_jobs == 0 are PE_OK (with n_jobs > 0
+ * and no pairs out_first is all -1).
+ * Read-only: the device residuals, the host mirror, the staged fit-mask state (pe_jobs_upload ...
+ * pe_fit_mask_rows) and pe_stats are left exactly as they are, and the call keeps nothing that a later
+ * pe_update_nodes or pe_load_nodes could invalidate.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): everything
+ * pe_place_greedy_domains refuses about the groups, the hierarchy and level; a NULL pair_job or pair_domain
+ * with n_pairs > 0; n_pairs outside [0, 2^31 - 1); a pair_job outside [0, n_jobs); a pair_domain outside
+ * [0, level_size[level]).  PE_ESTATE: a call before pe_load_nodes.  PE_ENOMEM: the working copies of
+ * domains too large for the workgroup's local memory could not be allocated (at most four times the shard's
+ * nodes x 32 B, whatever n_pairs is). */
+int pe_gang_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off /*[J+1]*/,
+                        const int32_t* group_count /*[G]*/, const int64_t* group_req /*[G][4]*/,
+                        const uint32_t* group_need /*[G] or NULL = 0*/,
+                        int64_t n_pairs, const int32_t* pair_job /*[P]*/, const int32_t* pair_domain /*[P]*/,
+                        int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                        const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                        uint8_t* out_fits /*[P] or NULL*/, int32_t* out_fail_group /*[P] or NULL*/,
+                        int64_t* out_pods /*[P] or NULL*/, int32_t* out_first /*[J] or NULL*/);
 
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one

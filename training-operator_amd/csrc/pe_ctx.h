@@ -1,5 +1,5 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp, pe_engine_place.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
+// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
 // the context itself.  Not part of the ABI.
 #pragma once
 
@@ -400,6 +400,20 @@ struct pe_ctx {
   DevBuf<int32_t> pl_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
   DevBuf<int64_t> pl_seg;       // the segments' residuals [4][stride]
   DevBuf<uint32_t> pl_segw;     // their global ids and labels, [2][stride]
+  // exact what-if of a gang per domain (pe_gang_fit_domains, pe_engine_fit.cpp).  As pl_*: every call sizes and
+  // fills what it uses, nothing of the hierarchy, the batch or the pair list outlives a call.  Grow and are reused.
+  HostBuf<uint8_t> ft_hin;      // one copy in: G PlaceGroup, P FitPair, U FitUnit, then leaf_dom and act_of
+  DevBuf<uint8_t> ft_in;
+  DevBuf<uint8_t> ft_out;       // one copy out: out_first [J], then out_fits, out_fail_group, out_pods [P] (16-B aligned)
+  HostBuf<uint8_t> ft_hout;
+  DevBuf<int32_t> ft_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
+  DevBuf<int64_t> ft_seg;       // the segments' residuals [4][stride], read-only to the fit kernels
+  DevBuf<uint32_t> ft_segw;     // their global ids and labels, [2][stride]
+  HostBuf<int32_t> ft_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
+  hipEvent_t ft_ev = nullptr;   // ... and the event behind that copy: the host waits for it, not for the units behind it
+  HostBuf<uint8_t> ft_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
+  DevBuf<uint8_t> ft_large;
+  DevBuf<int64_t> ft_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -475,6 +489,9 @@ struct pe_ctx {
     lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release();
     pl_hin.release(); pl_in.release(); pl_out.release(); pl_hout.release(); pl_log.release(); pl_dom.release();
     pl_seg.release(); pl_segw.release();
+    ft_hin.release(); ft_in.release(); ft_out.release(); ft_hout.release(); ft_dom.release(); ft_seg.release();
+    ft_segw.release(); ft_hoff.release(); ft_hlarge.release(); ft_large.release(); ft_scratch.release();
+    if (ft_ev) (void)hipEventDestroy(ft_ev);
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -549,9 +566,10 @@ inline void need_ptr(const void* p, const char* name) {
   if (!p) raise(PE_EINVAL, std::string(name) + " is NULL");
 }
 
-// PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity*_latency.py, tools/place_domains_latency.py): hipEvents on
-// the context's stream around a call's kernels; a successful call then leaves "S=<shapes> [P=<picks>]
-// kernels_ms=<time>" (the capacity calls) or "A=<active domains> kernels_ms=<time>" (pe_place_greedy_domains) in
+// PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity*_latency.py, tools/place_domains_latency.py,
+// tools/gang_fit_latency.py): hipEvents on the context's stream around a call's kernels; a successful call then
+// leaves "S=<shapes> [P=<picks>] kernels_ms=<time>" (the capacity calls), "A=<active domains> kernels_ms=<time>"
+// (pe_place_greedy_domains) or "A=<active domains> U=<units> kernels_ms=<time>" (pe_gang_fit_domains) in
 // pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
 // it on and off inside one process.
 struct CapEvents {
@@ -619,6 +637,12 @@ int64_t first_bad(int64_t n, Bad bad) {
 // (pe_engine.cpp)
 void check_req(const int64_t* req, int64_t n, const char* what);
 void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* what);
+// (pe_engine_place.cpp) What pe_place_greedy checks of a batch's groups (n_jobs > 0): the offsets, the counts
+// and the requests, with the first offending index; returns G.  And a refused hierarchy (pe_tree_plan.h
+// TreePlanError, `bad` its index) in pe_gang_capacity_tree's words.
+int64_t check_gang_groups(int64_t n_jobs, const int32_t* job_group_off, const int32_t* group_count,
+                          const int64_t* group_req);
+[[noreturn]] void raise_tree(int tree_error, int64_t bad);
 
 inline void fill_req(ReqRec& r, const int64_t* q, uint32_t need) {
   std::memset(&r, 0, sizeof(r));

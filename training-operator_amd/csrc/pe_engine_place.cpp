@@ -9,6 +9,37 @@
 
 static_assert(pe::DM_MAX_DOMAINS == PE_MAX_DOMAINS, "PE_MAX_DOMAINS");
 
+namespace pe_engine {
+
+int64_t check_gang_groups(int64_t n_jobs, const int32_t* job_group_off, const int32_t* group_count,
+                          const int64_t* group_req) {
+  if (n_jobs > (int64_t)INT32_MAX) raise(PE_EINVAL, "n_jobs above 2^31 - 1");
+  need_ptr(job_group_off, "job_group_off");
+  check_offsets(job_group_off, n_jobs, -1, "job_group_off");
+  const int64_t G = job_group_off[n_jobs];
+  if (G > 0) {
+    need_ptr(group_count, "group_count");
+    need_ptr(group_req, "group_req");
+    check_req(group_req, G, "group_req");
+    const int64_t i = first_bad(G, [group_count](int64_t g) { return group_count[g] < 0; });
+    if (i < G) raise(PE_EINVAL, "group_count: negative value at index " + std::to_string(i));
+  }
+  return G;
+}
+
+void raise_tree(int tree_error, int64_t bad) {
+  switch (tree_error) {
+    case pe::TREE_BAD_LEVELS: raise(PE_EINVAL, "n_levels outside [1, PE_MAX_LEVELS]");
+    case pe::TREE_NO_SIZES: raise(PE_EINVAL, "level_size is NULL");
+    case pe::TREE_BAD_SIZE:
+      raise(PE_EINVAL, "level_size: value outside [1, PE_MAX_DOMAINS] at index " + std::to_string(bad));
+    case pe::TREE_NO_PARENT: raise(PE_EINVAL, "parent is NULL with n_levels > 1");
+    default: raise(PE_EINVAL, "parent: value outside [-1, size of the level above) at index " + std::to_string(bad));
+  }
+}
+
+}  // namespace pe_engine
+
 namespace {
 
 // What pe_place_greedy checks of a batch (n_jobs > 0), with the first offending index; returns G.
@@ -19,17 +50,8 @@ int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const in
   need_ptr(job_group_off, "job_group_off");
   need_ptr(priority, "priority");
   need_ptr(out_job_status, "out_job_status");
-  check_offsets(job_group_off, n_jobs, -1, "job_group_off");
-  const int64_t G = job_group_off[n_jobs];
-  bool pods = false;
-  if (G > 0) {
-    need_ptr(group_count, "group_count");
-    need_ptr(group_req, "group_req");
-    check_req(group_req, G, "group_req");
-    const int64_t i = first_bad(G, [group_count](int64_t g) { return group_count[g] < 0; });
-    if (i < G) raise(PE_EINVAL, "group_count: negative value at index " + std::to_string(i));
-    pods = first_bad(G, [group_count](int64_t g) { return group_count[g] > 0; }) < G;
-  }
+  const int64_t G = check_gang_groups(n_jobs, job_group_off, group_count, group_req);
+  const bool pods = first_bad(G, [group_count](int64_t g) { return group_count[g] > 0; }) < G;
   if (pods) need_ptr(out_pod_node, "out_pod_node");
   return G;
 }
@@ -40,15 +62,7 @@ int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const in
     case pe::PLACE_NO_DOMAINS: raise(PE_EINVAL, "job_domain is NULL");
     case pe::PLACE_BAD_DOMAIN:
       raise(PE_EINVAL, "job_domain: value outside [0, level_size[level]) at index " + std::to_string(bad));
-    default: break;
-  }
-  switch (te) {   // the hierarchy, in pe_gang_capacity_tree's words
-    case pe::TREE_BAD_LEVELS: raise(PE_EINVAL, "n_levels outside [1, PE_MAX_LEVELS]");
-    case pe::TREE_NO_SIZES: raise(PE_EINVAL, "level_size is NULL");
-    case pe::TREE_BAD_SIZE:
-      raise(PE_EINVAL, "level_size: value outside [1, PE_MAX_DOMAINS] at index " + std::to_string(bad));
-    case pe::TREE_NO_PARENT: raise(PE_EINVAL, "parent is NULL with n_levels > 1");
-    default: raise(PE_EINVAL, "parent: value outside [-1, size of the level above) at index " + std::to_string(bad));
+    default: raise_tree(te, bad);   // the hierarchy, in pe_gang_capacity_tree's words
   }
 }
 

@@ -1,6 +1,6 @@
 // Device-side building blocks of libplacement (gfx950).  Host code in pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp and pe_engine_place.cpp launches these through the wrappers below; nothing here is part
-// of the C ABI.
+// pe_engine_capacity.cpp, pe_engine_place.cpp and pe_engine_fit.cpp launches these through the wrappers below;
+// nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -557,5 +557,32 @@ hipError_t launch_place_members(hipStream_t s, const int64_t* res, int64_t strid
 hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* job_start,
                                 int A, const PlaceSegs& segs, int64_t* res, int64_t stride, uint64_t id_base,
                                 int32_t* out_pod, int32_t* out_status, int32_t* log);
+
+// ---- exact what-if of a whole gang per domain (pe_gang_fit_domains, pe_fit.hip; the plan and its FitUnit /
+// FitLarge records: pe_fit_plan.h).  The member lists are launch_place_members', read-only here.
+struct FitUnit;
+struct FitLarge;
+// One (job, domain) pair in plan order: its index in the caller's list, its job and the job's groups [g0, g1).
+struct FitPair {
+  int32_t pair, job, g0, g1;
+};
+static_assert(sizeof(FitPair) == 16, "FitPair must be 16 B");
+// The answers of a call, on the device: first[J] (the caller sets every cell to -1; unsigned minimum of the
+// fitting pairs' indices), and per pair fits, fail_group and pods, by the caller's pair index.
+struct FitOut {
+  uint32_t* first;
+  uint8_t* fits;
+  int32_t* fail_group;
+  int64_t* pods;
+};
+// One workgroup per unit u < U; those whose segment has at most PL_LDS_NODES nodes judge their pairs on a working
+// copy in LDS, the others leave at once.  PlaceGroup.pod0 is not read.
+hipError_t launch_fit_units(hipStream_t s, const PlaceGroup* groups, const FitPair* pairs, const FitUnit* units, int64_t U,
+                            const PlaceSegs& segs, const FitOut& out);
+// One workgroup per record of large[0 .. n_large): the units of a larger segment that the record names, on the
+// working copy scratch[at + d * n] (n = the segment's nodes).
+hipError_t launch_fit_large(hipStream_t s, const PlaceGroup* groups, const FitPair* pairs, const FitUnit* units,
+                            const FitLarge* large, int64_t n_large, int64_t* scratch, const PlaceSegs& segs,
+                            const FitOut& out);
 
 }  // namespace pe

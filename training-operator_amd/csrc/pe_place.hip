@@ -11,7 +11,8 @@
 // bits), so no result depends on that order.  A domain without nodes has a zero-length segment and still
 // gets its workgroup, which fails the jobs that have pods and passes the others.
 //
-// place_domains_kernel: the workgroup walks its jobs in plan order, group by group.  Per decision every
+// place_domains_kernel: the workgroup walks its jobs in plan order, group by group.  The decision itself is
+// pe_place_step.h's, shared with the read-only what-if of pe_fit.hip.  Per decision every
 // thread scores its share of the segment with node_key (pe_node_key.h) against the working residuals and
 // finds what its own best node would take; a wave butterfly (pe_wave.h) and one cross-wave step through LDS
 // give the block's minimum key with that node's place and take.  The chosen node takes
@@ -30,16 +31,13 @@
 #include <type_traits>
 
 #include "pe_kernels.h"
-#include "pe_node_key.h"
-#include "pe_wave.h"
+#include "pe_place_step.h"
 
 namespace pe {
 
 namespace {
 
 constexpr int PM_THREADS = 256;
-constexpr int PL_WAVES = PL_THREADS / 64;
-constexpr uint32_t NEED_ISLAND = 0x80000000u;   // PE_NEED_ISLAND
 
 // The active index of local node n, -1 for none.
 __device__ __forceinline__ int node_active(const int32_t* __restrict__ island, int64_t n,
@@ -116,29 +114,6 @@ __global__ __launch_bounds__(PM_THREADS) void place_fill_kernel(
   for (int d = 0; d < D; ++d) sg.res[d * sg.seg_stride + at] = res[d * stride + n];
 }
 
-// What node state (r0 .. r3) takes of `left` pods of request q: min(left, min over q_d > 0 of floor(r_d / q_d)).
-// Called for a node that fits one pod, so every r_d >= q_d >= 0.
-__device__ __forceinline__ uint32_t take_of(int64_t r0, int64_t r1, int64_t r2, int64_t r3, int64_t q0, int64_t q1,
-                                            int64_t q2, int64_t q3, uint32_t left) {
-  uint64_t t = left;
-  if (q0 > 0) t = min(t, (uint64_t)r0 / (uint64_t)q0);
-  if (q1 > 0) t = min(t, (uint64_t)r1 / (uint64_t)q1);
-  if (q2 > 0) t = min(t, (uint64_t)r2 / (uint64_t)q2);
-  if (q3 > 0) t = min(t, (uint64_t)r3 / (uint64_t)q3);
-  return (uint32_t)t;
-}
-
-struct PlaceShared {   // the global segment's shape with a stride of PL_LDS_NODES
-  int64_t r[D][PL_LDS_NODES];
-  uint32_t gid[PL_LDS_NODES];
-  uint32_t lab[PL_LDS_NODES];
-};
-struct PlaceMin {   // the waves' minima of a decision, two sets used in turn: one barrier per decision
-  uint64_t key[2][PL_WAVES];
-  uint32_t at[2][PL_WAVES];
-  uint32_t take[2][PL_WAVES];
-};
-
 // A failed job gives back what it took: its n_log log entries (place, group, pods) added back to the working
 // state r[d * rs + place] and its n_pods pod slots set to -1.  Out of line, on generic pointers (the state is in
 // LDS or global memory): the path is cold, and inlined its uniform values cost the decision loop SGPRs.
@@ -164,7 +139,7 @@ __device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, S
                                              const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs,
                                              int j0, int j1, int32_t* __restrict__ out_pod,
                                              int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int64_t* const r1 = r0 + rs;
   int64_t* const r2 = r1 + rs;
   int64_t* const r3 = r2 + rs;
@@ -185,61 +160,20 @@ __device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, S
       if (gr.count <= 0) continue;
       const bool unit = (gr.need & NEED_ISLAND) != 0;   // an island group: one decision for count x request
       int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];   // the request the scan scores
-      if (unit) {
-        bool ovf = __builtin_mul_overflow(gr.q[0], (int64_t)gr.count, &s0);
-        ovf |= __builtin_mul_overflow(gr.q[1], (int64_t)gr.count, &s1);
-        ovf |= __builtin_mul_overflow(gr.q[2], (int64_t)gr.count, &s2);
-        ovf |= __builtin_mul_overflow(gr.q[3], (int64_t)gr.count, &s3);
-        if (ovf) {   // fits nowhere
-          ok = false;
-          break;
-        }
+      if (unit && !island_request(gr, s0, s1, s2, s3)) {   // fits nowhere
+        ok = false;
+        break;
       }
       uint32_t left = (uint32_t)gr.count;
       int64_t slot = gr.pod0;
       while (left > 0) {
-        uint64_t bk = NO_KEY;
-        uint32_t bi = 0, bt = 0;
-        for (int i = tid; i < n; i += PL_THREADS) {
-          const uint64_t k = node_key(r0[i], r1[i], r2[i], r3[i], lab[i], s0, s1, s2, s3, gr.need, gid[i]);
-          if (k < bk) {
-            bk = k;
-            bi = (uint32_t)i;
-          }
-        }
-        if (bk != NO_KEY) bt = unit ? left : take_of(r0[bi], r1[bi], r2[bi], r3[bi], s0, s1, s2, s3, left);
-        wave_argmin_u64(bk, bi, bt);
-        if (lane == 0) {
-          mn.key[par][wave] = bk;
-          mn.at[par][wave] = bi;
-          mn.take[par][wave] = bt;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; ++w) {
-          const uint64_t k = mn.key[par][w];
-          if (w == 0 || k < bk) {
-            bk = k;
-            bi = mn.at[par][w];
-            bt = mn.take[par][w];
-          }
-        }
-        par ^= 1;
-        // the same on every thread; said so for the branches and barriers that follow
-        const uint32_t klo = __builtin_amdgcn_readfirstlane((uint32_t)bk);
-        const uint32_t khi = __builtin_amdgcn_readfirstlane((uint32_t)(bk >> 32));
-        const uint32_t at = __builtin_amdgcn_readfirstlane(bi), t = __builtin_amdgcn_readfirstlane(bt);
-        if ((klo & khi) == 0xFFFFFFFFu) {   // NO_KEY: no node of the domain fits
+        const PlaceChoice c = place_decide(r0, r1, r2, r3, gid, lab, n, s0, s1, s2, s3, gr.need, unit, left, mn, par);
+        if (c.none()) {   // no node of the domain fits
           ok = false;
           break;
         }
-        if ((at & (PL_THREADS - 1)) == (uint32_t)tid) {   // the place's owner; m * s_d <= r_d
-          const int64_t m = unit ? 1 : (int64_t)t;           // (unit: s = count x request, t = count)
-          r0[at] -= m * s0;
-          r1[at] -= m * s1;
-          r2[at] -= m * s2;
-          r3[at] -= m * s3;
-        }
+        place_take(r0, r1, r2, r3, c, unit, s0, s1, s2, s3);
+        const uint32_t at = c.at, t = c.t;
         if (tid == 0) {   // n_log < the pods the job placed so far, this decision's included
           int32_t* const e = log + 3 * (pod0 + n_log);
           e[0] = (int32_t)at;
@@ -247,7 +181,7 @@ __device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, S
           e[2] = (int32_t)t;
         }
         ++n_log;
-        const int32_t node = (int32_t)(klo & 0xFFFFFFu);
+        const int32_t node = (int32_t)(c.klo & 0xFFFFFFu);
         for (int64_t p = slot + tid; p < slot + t; p += PL_THREADS) out_pod[p] = node;   // slot + t <= pod1 <= P
         slot += t;
         left -= t;

@@ -24,7 +24,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree"]
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit"]
 
 
 class PlacementError(RuntimeError):
@@ -108,6 +108,14 @@ class TreeCapacity(NamedTuple):
     domain: Optional[np.ndarray]         # int32 [J]: that level's domain with the smallest such slots, ties to the smallest id
     domain_slots: Optional[np.ndarray]   # int64 [J]: that domain's slots, 0 when none
     feasible: Optional[np.ndarray]       # int32 [J][n_levels]: domains of each level with slots >= count
+
+
+class GangFit(NamedTuple):
+    """Engine.gang_fit_domains' answer; a part that was not asked for is None."""
+    fits: Optional[np.ndarray]           # uint8 [P]: 1 = the job alone would be placed in the domain right now
+    fail_group: Optional[np.ndarray]     # int32 [P]: -1, or the first group (within the job) not placed in full
+    pods: Optional[np.ndarray]           # int64 [P]: pods the rule had placed when it stopped
+    first: Optional[np.ndarray]          # int32 [J]: the smallest fitting pair of job j, -1 = none
 
 
 def _level_sizes(level_size):
@@ -562,6 +570,36 @@ class Engine:
                                                    _p(nd), _p(dom), int(level), len(ls), _p(ls), _p(par), _p(pod),
                                                    _p(st)), "pe_place_greedy_domains")
         return pod[:P], st[:J]
+
+    def gang_fit_domains(self, job_group_off, group_count, group_req, group_need, pair_job, pair_domain, level,
+                         level_size, parent=None, tables=True, first=True) -> GangFit:
+        """pe_gang_fit_domains: for every pair p, would place_greedy_domains place job pair_job[p] ALONE in the
+        level-`level` domain pair_domain[p] against the current residuals?  Read-only.  The batch is place_greedy's
+        without priorities; level_size / parent describe the hierarchy exactly as for gang_capacity_tree.  The pairs
+        may come in any order and repeat.  tables=False leaves the three [P] answers out (they never cross),
+        first=False the per-job first fit in the caller's pair order."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        pj = _c(pair_job, np.int32).reshape(-1)
+        pd = _c(pair_domain, np.int32).reshape(-1)
+        if pj.shape != pd.shape:
+            raise ValueError("pair_job and pair_domain must have one length")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = len(pj)
+        fits = np.zeros(P, dtype=np.uint8) if tables else None
+        fail = np.full(P, -1, dtype=np.int32) if tables else None
+        pods = np.zeros(P, dtype=np.int64) if tables else None
+        fst = np.full(J, -1, dtype=np.int32) if first else None
+        self._chk(self.lib.pe_gang_fit_domains(self.h, J, _p(jgo), _p(cnt), _p(req), _p(nd), P, _p(pj), _p(pd), int(level),
+                                               len(ls), _p(ls), _p(par), _p(fits), _p(fail), _p(pods), _p(fst)),
+                  "pe_gang_fit_domains")
+        return GangFit(fits, fail, pods, fst)
 
     # ------------------------------------------------------------ misc
     def synchronize(self):
