@@ -776,6 +776,28 @@ func (e *Engine) GangFitDomains(g *Gangs, pairJob, pairDomain []int32, level int
 	return fits, failGroup, pods, first, e.err(rc, "pe_gang_fit_domains")
 }
 
+// PlaceFirstFitDomains places every job, in (priority desc, index asc) order, in the first of its candidate
+// domains -- its pairs in ascending p, as for GangFitDomains -- in which PlaceGreedyDomains would place it against
+// the residuals as the earlier jobs of the batch left them: the batch form of GangFitDomains followed by
+// PlaceGreedyDomains, exact where that pair of calls is not (every job there selects on the untouched residuals).
+// A job whose candidates all fail, or that is in no pair, is unschedulable.  jobPair[j] is the pair that placed job
+// j or -1.  levelSize and parent describe the hierarchy exactly as for GangCapacityTree.  Residuals are updated in
+// place.  A sharded engine refuses the call.
+func (e *Engine) PlaceFirstFitDomains(g *Gangs, pairJob, pairDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus, jobPair []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	P := len(pairJob)
+	if len(pairDomain) != P {
+		return nil, nil, nil, fmt.Errorf("PlaceFirstFitDomains: %d jobs for %d domains", P, len(pairDomain))
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	jobPair = make([]int32, J)
+	rc := C.pe_place_first_fit_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), C.int64_t(P), ptr32(pairJob), ptr32(pairDomain), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus), ptr32(jobPair))
+	return podNode, jobStatus, jobPair, e.err(rc, "pe_place_first_fit_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

@@ -530,6 +530,43 @@ int pe_gang_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_of
                         uint8_t* out_fits /*[P] or NULL*/, int32_t* out_fail_group /*[P] or NULL*/,
                         int64_t* out_pods /*[P] or NULL*/, int32_t* out_first /*[J] or NULL*/);
 
+/* (ABI 7, additive) First-fit placement of a batch over candidate domains: place each gang in the first of
+ * its candidate domains that still holds it.  The batch form of the chain pe_gang_capacity_tree ->
+ * pe_gang_fit_domains -> pe_place_greedy_domains, which is exact for one job at a time only: out_first is
+ * judged "with no other job in the call", so two jobs may both be told that rack 7 is their first fit when
+ * rack 7 holds one of them.  Here every job comes with an ordered list of candidate domains and is placed in
+ * the first that fits the residuals AS THE EARLIER JOBS OF THE BATCH LEFT THEM (Kueue's "required: rack, try
+ * these racks in this order").  NO reference function, as pe_place_greedy_domains.
+ * Groups, counts, requests, needs, priority, pod slots, out_job_status and the in-place residuals mean what
+ * they mean in pe_place_greedy_domains; levels, level_size, parent and dom_level(n) likewise; pair_job and
+ * pair_domain mean what they mean in pe_gang_fit_domains: any order, ungrouped, repeats allowed, a job may
+ * be in no pair.  A job's candidates are its pairs in ascending p.
+ * The rule: jobs are handled in (priority desc, index asc) order.  Job j tries its candidates in order; an
+ * attempt at pair p is exactly pe_place_greedy_domains on the single job j with job_domain = pair_domain[p],
+ * against the residuals as they stand after every earlier job of that order.  The first attempt that returns
+ * PE_JOB_PLACED stands: its pods stay and the residuals keep them.  A failed attempt is rolled back in full
+ * before the next one.  A job whose candidates all fail, or that is in no pair (whatever its groups), is
+ * PE_JOB_UNSCHEDULABLE with -1 in all its pod slots.  out_job_pair[j] = the pair that placed job j, or -1.
+ * Two identities follow: with exactly one pair per job every output equals pe_place_greedy_domains with
+ * job_domain[j] = pair_domain[pair of j]; with one job in the call out_job_pair[0] equals
+ * pe_gang_fit_domains' out_first[0] on the same residuals.
+ * The device runs the rule exactly, in rounds of one launch each, one workgroup per active domain; a
+ * workgroup never waits for another.  At most n_pairs + 1 rounds are launched; a
+ * batch that were not settled by then is PE_EHIP (never seen: the bound is proven).
+ * After the call the device residuals and the host mirror both hold the new residuals; pe_reset_residuals
+ * restores as usual and the staged fit batch stays valid.  pe_stats: adds to pods_placed, jobs_placed and
+ * jobs_failed only.  n_jobs == 0 is PE_OK; n_pairs == 0 with jobs is PE_OK with every job unschedulable.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there
+ * is one): everything pe_place_greedy_domains refuses about the batch, the hierarchy and level, and
+ * everything pe_gang_fit_domains refuses about the pairs.  PE_ESTATE: a call before pe_load_nodes. */
+int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                               const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                               int64_t n_pairs, const int32_t* pair_job /*[P]*/, const int32_t* pair_domain /*[P]*/,
+                               int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                               const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                               int32_t* out_pod_node, int32_t* out_job_status, int32_t* out_job_pair /*[J] or NULL*/);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

@@ -414,6 +414,19 @@ struct pe_ctx {
   HostBuf<uint8_t> ft_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
   DevBuf<uint8_t> ft_large;
   DevBuf<int64_t> ft_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
+  // first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_engine_first_fit.cpp).
+  // As pl_*: every call sizes and fills them anew.
+  HostBuf<uint8_t> ff_hin;      // one copy in: G PlaceGroup, J PlaceJob (by job index), P FirstFitEntry, then
+  DevBuf<uint8_t> ff_in;        // leaf_dom, act_of and q_start
+  DevBuf<int32_t> ff_out;       // one copy out: out_pod_node [P], then out_job_status [J] and out_job_pair [J]
+  HostBuf<int32_t> ff_hout;
+  DevBuf<int32_t> ff_log;       // the jobs' rollback logs, [P][3]
+  DevBuf<int32_t> ff_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
+  DevBuf<int64_t> ff_seg;       // the segments' residuals [4][stride]: the working residuals between rounds
+  DevBuf<uint32_t> ff_segw;     // their global ids and labels, [2][stride]
+  DevBuf<uint64_t> ff_state;    // the rounds' state: the jobs' words [J], the unsettled count, the queue cursors [A]
+  HostBuf<uint32_t> ff_hopen;   // the unsettled count read back
+  HostBuf<int32_t> ff_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -491,6 +504,8 @@ struct pe_ctx {
     pl_seg.release(); pl_segw.release();
     ft_hin.release(); ft_in.release(); ft_out.release(); ft_hout.release(); ft_dom.release(); ft_seg.release();
     ft_segw.release(); ft_hoff.release(); ft_hlarge.release(); ft_large.release(); ft_scratch.release();
+    ff_hin.release(); ff_in.release(); ff_out.release(); ff_hout.release(); ff_log.release(); ff_dom.release();
+    ff_seg.release(); ff_segw.release(); ff_state.release(); ff_hopen.release(); ff_hoff.release();
     if (ft_ev) (void)hipEventDestroy(ft_ev);
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
@@ -567,10 +582,11 @@ inline void need_ptr(const void* p, const char* name) {
 }
 
 // PE_CAP_EVENTS=1 (diagnostics, tools/gang_capacity*_latency.py, tools/place_domains_latency.py,
-// tools/gang_fit_latency.py): hipEvents on the context's stream around a call's kernels; a successful call then
-// leaves "S=<shapes> [P=<picks>] kernels_ms=<time>" (the capacity calls), "A=<active domains> kernels_ms=<time>"
-// (pe_place_greedy_domains) or "A=<active domains> U=<units> kernels_ms=<time>" (pe_gang_fit_domains) in
-// pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
+// tools/gang_fit_latency.py, tools/first_fit_latency.py): hipEvents on the context's stream around a call's
+// kernels; a successful call then leaves "S=<shapes> [P=<picks>] kernels_ms=<time>" (the capacity calls),
+// "A=<active domains> kernels_ms=<time>" (pe_place_greedy_domains), "A=<active domains> U=<units>
+// kernels_ms=<time>" (pe_gang_fit_domains) or "A=<active domains> rounds=<rounds launched> kernels_ms=<time>"
+// (pe_place_first_fit_domains) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
 // it on and off inside one process.
 struct CapEvents {
   pe_ctx* ctx;
@@ -643,6 +659,10 @@ void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* wha
 int64_t check_gang_groups(int64_t n_jobs, const int32_t* job_group_off, const int32_t* group_count,
                           const int64_t* group_req);
 [[noreturn]] void raise_tree(int tree_error, int64_t bad);
+// (pe_engine_place.cpp) What pe_place_greedy_domains checks of a batch (n_jobs > 0) and its outputs; returns G.
+int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                          const int32_t* group_count, const int64_t* group_req, const int32_t* out_pod_node,
+                          const int32_t* out_job_status);
 
 inline void fill_req(ReqRec& r, const int64_t* q, uint32_t need) {
   std::memset(&r, 0, sizeof(r));

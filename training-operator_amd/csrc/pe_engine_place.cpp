@@ -38,10 +38,6 @@ void raise_tree(int tree_error, int64_t bad) {
   }
 }
 
-}  // namespace pe_engine
-
-namespace {
-
 // What pe_place_greedy checks of a batch (n_jobs > 0), with the first offending index; returns G.
 int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
                           const int32_t* group_count, const int64_t* group_req, const int32_t* out_pod_node,
@@ -55,6 +51,10 @@ int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const in
   if (pods) need_ptr(out_pod_node, "out_pod_node");
   return G;
 }
+
+}  // namespace pe_engine
+
+namespace {
 
 [[noreturn]] void raise_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad) {
   switch (e) {

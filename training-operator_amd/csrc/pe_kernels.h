@@ -558,6 +558,40 @@ hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const P
                                 int A, const PlaceSegs& segs, int64_t* res, int64_t stride, uint64_t id_base,
                                 int32_t* out_pod, int32_t* out_status, int32_t* log);
 
+// ---- first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_place.hip; the plan:
+// pe_first_fit_plan.h).  The member lists are launch_place_members'; the segments stay the working residuals of
+// their domains from round to round.
+// One entry of an active domain's queue: candidate k of `job` (its pair `pair` of the caller's list), last = 1
+// when k is the job's last candidate.  A queue is sorted by (the job's rank in the job order, k).
+struct FirstFitEntry {
+  int32_t job, k, pair, last;
+};
+static_assert(sizeof(FirstFitEntry) == 16, "FirstFitEntry must be 16 B");
+constexpr uint32_t FF_SETTLED = 0x80000000u;
+// The state the rounds carry.  word[J]: per job, low half = the position k of the candidate it tries next, with
+// FF_SETTLED set once it is placed or out of candidates (k then the position of its last attempt), high half =
+// the round that wrote the word; the caller zeroes it.  cursor[A]: per active domain the next entry of its
+// queue, set to q_start[a] by the caller.  open: the jobs not yet settled, set by the caller to the number of
+// jobs with a candidate.
+struct FirstFitState {
+  uint64_t* word;
+  int32_t* cursor;
+  uint32_t* open;
+};
+// Round `round` (1, 2, ...): one workgroup per active domain works off the head of its queue as far as the words
+// AS THEY STOOD WHEN THE ROUND BEGAN allow and returns.  jobs[J] by the caller's job index.  out_pod [P] and
+// out_pair [J] preset to -1 and out_status [J] to 1 by the caller; log as for launch_place_domains.  kinds: which
+// of the two kernel instances to launch, FF_SMALL for the segments of at most PL_LDS_NODES nodes, FF_LARGE for
+// the larger ones; a caller who does not know the segments' sizes passes both.
+constexpr int FF_SMALL = 1, FF_LARGE = 2;
+hipError_t launch_first_fit_round(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* q_start,
+                                  const FirstFitEntry* queue, int A, const PlaceSegs& segs, int kinds, uint32_t round,
+                                  const FirstFitState& st, int32_t* out_pod, int32_t* out_status, int32_t* out_pair,
+                                  int32_t* log);
+// The segments' residuals back to the live SoA, once, after the last round.
+hipError_t launch_first_fit_finish(hipStream_t s, const PlaceSegs& segs, int A, int64_t Ns, int64_t* res, int64_t stride,
+                                   uint64_t id_base);
+
 // ---- exact what-if of a whole gang per domain (pe_gang_fit_domains, pe_fit.hip; the plan and its FitUnit /
 // FitLarge records: pe_fit_plan.h).  The member lists are launch_place_members', read-only here.
 struct FitUnit;

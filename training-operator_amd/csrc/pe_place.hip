@@ -26,6 +26,9 @@
 // and its pod slots become -1.  The working state lives in LDS for segments up to PL_LDS_NODES nodes and in
 // the global segment beyond (two instances of the kernel, each taking its kind of segment); at the end the
 // workgroup writes its nodes' residuals back to the live SoA.
+//
+// first_fit_round_kernel (pe_place_first_fit_domains): the same decisions job by job (place_job), with every job
+// free to move on to its next candidate domain; the comment at first_fit_queue has the scheme.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -133,18 +136,72 @@ __device__ __noinline__ void place_rollback(int64_t* r, int64_t rs, const PlaceG
   for (int64_t p = tid; p < n_pods; p += PL_THREADS) pods[p] = -1;
 }
 
-// One domain's jobs on its n nodes, whose working state is r[d * rs + i] (written), gid[i] and labels gid[rs + i].
+// One job (groups [g0, g1), g0 < g1) on a domain's n nodes, whose working state is r[d * rs + i] (written), gid[i]
+// and labels gid[rs + i]: whether it is placed, the same on every thread.  A job that is not gives back what it
+// took before the call returns.  `par`: place_decide's, carried from job to job.
 template <class Stride>
-__device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, Stride rs, int n, PlaceMin& mn,
-                                             const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs,
-                                             int j0, int j1, int32_t* __restrict__ out_pod,
-                                             int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
+__device__ __forceinline__ bool place_job(int64_t* r0, const uint32_t* gid, Stride rs, int n, PlaceMin& mn, int& par,
+                                          const PlaceGroup* __restrict__ groups, int g0, int g1,
+                                          int32_t* __restrict__ out_pod, int32_t* __restrict__ log) {
   const int tid = threadIdx.x;
   int64_t* const r1 = r0 + rs;
   int64_t* const r2 = r1 + rs;
   int64_t* const r3 = r2 + rs;
   const uint32_t* const lab = gid + rs;
   // log entry e, three words at log[3 e]: its place in the segment, its group, the pods it placed
+  const int64_t pod0 = groups[g0].pod0;   // the job's pod slots: [pod0, the last group's pod0 + count)
+  int64_t n_log = 0;   // entries of this job, at log[pod0 ..]; <= the pods it placed
+  bool ok = true;
+  for (int g = g0; g < g1 && ok; ++g) {
+    const PlaceGroup gr = groups[g];
+    if (gr.count <= 0) continue;
+    const bool unit = (gr.need & NEED_ISLAND) != 0;   // an island group: one decision for count x request
+    int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];   // the request the scan scores
+    if (unit && !island_request(gr, s0, s1, s2, s3)) {   // fits nowhere
+      ok = false;
+      break;
+    }
+    uint32_t left = (uint32_t)gr.count;
+    int64_t slot = gr.pod0;
+    while (left > 0) {
+      const PlaceChoice c = place_decide(r0, r1, r2, r3, gid, lab, n, s0, s1, s2, s3, gr.need, unit, left, mn, par);
+      if (c.none()) {   // no node of the domain fits
+        ok = false;
+        break;
+      }
+      place_take(r0, r1, r2, r3, c, unit, s0, s1, s2, s3);
+      const uint32_t at = c.at, t = c.t;
+      if (tid == 0) {   // n_log < the pods the job placed so far, this decision's included
+        int32_t* const e = log + 3 * (pod0 + n_log);
+        e[0] = (int32_t)at;
+        e[1] = g;
+        e[2] = (int32_t)t;
+      }
+      ++n_log;
+      const int32_t node = (int32_t)(c.klo & 0xFFFFFFu);
+      for (int64_t p = slot + tid; p < slot + t; p += PL_THREADS) out_pod[p] = node;   // slot + t <= pod1 <= P
+      slot += t;
+      left -= t;
+    }
+  }
+  if (!ok) {
+    // every update and pod store of this job lies before the barrier of the decision that failed -- or,
+    // for an overflowing island group, before this one
+    __syncthreads();
+    place_rollback(r0, (int64_t)rs, groups, log + 3 * pod0, n_log, out_pod + pod0,
+                   groups[g1 - 1].pod0 + groups[g1 - 1].count - pod0);
+    __syncthreads();   // the owners read their places again
+  }
+  return ok;
+}
+
+// One domain's jobs jobs[j0 .. j1), in that order, on its n nodes (the working state as for place_job).
+template <class Stride>
+__device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, Stride rs, int n, PlaceMin& mn,
+                                             const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs,
+                                             int j0, int j1, int32_t* __restrict__ out_pod,
+                                             int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
+  const int tid = threadIdx.x;
   int par = 0;
   for (int ji = j0; ji < j1; ++ji) {
     const int g0 = jobs[ji].g0, g1 = jobs[ji].g1;
@@ -152,49 +209,7 @@ __device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, S
       if (tid == 0) out_status[jobs[ji].job] = 0;
       continue;
     }
-    const int64_t pod0 = groups[g0].pod0;   // the job's pod slots: [pod0, the last group's pod0 + count)
-    int64_t n_log = 0;   // entries of this job, at log[pod0 ..]; <= the pods it placed
-    bool ok = true;
-    for (int g = g0; g < g1 && ok; ++g) {
-      const PlaceGroup gr = groups[g];
-      if (gr.count <= 0) continue;
-      const bool unit = (gr.need & NEED_ISLAND) != 0;   // an island group: one decision for count x request
-      int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];   // the request the scan scores
-      if (unit && !island_request(gr, s0, s1, s2, s3)) {   // fits nowhere
-        ok = false;
-        break;
-      }
-      uint32_t left = (uint32_t)gr.count;
-      int64_t slot = gr.pod0;
-      while (left > 0) {
-        const PlaceChoice c = place_decide(r0, r1, r2, r3, gid, lab, n, s0, s1, s2, s3, gr.need, unit, left, mn, par);
-        if (c.none()) {   // no node of the domain fits
-          ok = false;
-          break;
-        }
-        place_take(r0, r1, r2, r3, c, unit, s0, s1, s2, s3);
-        const uint32_t at = c.at, t = c.t;
-        if (tid == 0) {   // n_log < the pods the job placed so far, this decision's included
-          int32_t* const e = log + 3 * (pod0 + n_log);
-          e[0] = (int32_t)at;
-          e[1] = g;
-          e[2] = (int32_t)t;
-        }
-        ++n_log;
-        const int32_t node = (int32_t)(c.klo & 0xFFFFFFu);
-        for (int64_t p = slot + tid; p < slot + t; p += PL_THREADS) out_pod[p] = node;   // slot + t <= pod1 <= P
-        slot += t;
-        left -= t;
-      }
-    }
-    if (!ok) {
-      // every update and pod store of this job lies before the barrier of the decision that failed -- or,
-      // for an overflowing island group, before this one
-      __syncthreads();
-      place_rollback(r0, (int64_t)rs, groups, log + 3 * pod0, n_log, out_pod + pod0,
-                     groups[g1 - 1].pod0 + groups[g1 - 1].count - pod0);
-      __syncthreads();   // the owners read their places again
-    }
+    const bool ok = place_job(r0, gid, rs, n, mn, par, groups, g0, g1, out_pod, log);
     if (tid == 0) out_status[jobs[ji].job] = ok ? 0 : 1;
   }
 }
@@ -250,6 +265,110 @@ __global__ __launch_bounds__(PL_THREADS) void place_domains_kernel(
   }
 }
 
+// ---- pe_place_first_fit_domains: one round.  The workgroup of active domain a looks at the head of its queue.
+// Whatever it reads of another job's word it reads as the word stood when the round began: a word stamped with
+// this round was written by an attempt at position k' of this very round (a job is attempted at most once per
+// round: its stamped word stops every other entry of it), so the value before was k', unsettled.  An entry whose
+// job has moved past it is skipped, an entry whose job is due here is attempted -- place_job's decisions and
+// rollback -- and an entry whose job is still busy elsewhere ends the round for this domain.  Nothing depends on
+// which workgroup ran first, nobody waits for anybody, and pods, residuals and logs pass from workgroup to
+// workgroup only across the kernel boundary.  The head of the queue has the lowest rank among the entries still
+// open at this domain, so an attempt sees the domain as the sequential rule leaves it.
+template <class Stride, class Stage>
+__device__ __forceinline__ bool first_fit_queue(int64_t* r0, const uint32_t* gid, Stride rs, int n, PlaceMin& mn,
+                                                uint64_t* head, const PlaceGroup* __restrict__ groups,
+                                                const PlaceJob* __restrict__ jobs,
+                                                const FirstFitEntry* __restrict__ queue, int cur, int end, int a,
+                                                uint32_t round, const FirstFitState& st, int32_t* __restrict__ out_pod,
+                                                int32_t* __restrict__ out_status, int32_t* __restrict__ out_pair,
+                                                int32_t* __restrict__ log, Stage stage) {
+  const int tid = threadIdx.x;
+  int par = 0, hp = 0;
+  bool staged = false;
+  for (; cur < end; ++cur) {
+    const FirstFitEntry e = queue[cur];
+    if (tid == 0) head[hp] = __hip_atomic_load(&st.word[e.job], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();   // head[] is used in turn, as PlaceMin's sets are: one barrier per entry
+    const uint64_t w = head[hp];
+    hp ^= 1;
+    const uint32_t stamp = (uint32_t)(w >> 32);
+    uint32_t ptr = (uint32_t)w;
+    if (stamp == round) ptr = (ptr & FF_SETTLED) ? (ptr & ~FF_SETTLED) : ptr - 1;   // as the round began
+    if ((ptr & FF_SETTLED) || ptr > (uint32_t)e.k) continue;   // settled, or past this candidate
+    if (ptr < (uint32_t)e.k || stamp == round) break;          // busy elsewhere: the next round's
+    if (!staged) {
+      stage();
+      staged = true;
+    }
+    const PlaceJob pj = jobs[e.job];
+    const bool ok = pj.g0 == pj.g1 || place_job(r0, gid, rs, n, mn, par, groups, pj.g0, pj.g1, out_pod, log);
+    if (tid == 0) {
+      uint32_t next = (uint32_t)e.k + 1;
+      if (ok) {
+        out_status[e.job] = 0;
+        out_pair[e.job] = e.pair;
+      }
+      if (ok || e.last) {
+        next = FF_SETTLED | (uint32_t)e.k;
+        atomicSub(st.open, 1u);
+      }
+      __hip_atomic_store(&st.word[e.job], ((uint64_t)round << 32) | next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if (tid == 0) st.cursor[a] = cur;
+  return staged;
+}
+
+// IN_LDS as for place_domains_kernel: the segments of at most PL_LDS_NODES nodes are staged in LDS before the
+// round's first attempt and written back to the segment after its last; the larger ones are worked on in place.
+template <bool IN_LDS>
+__global__ __launch_bounds__(PL_THREADS) void first_fit_round_kernel(
+    const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs, const int32_t* __restrict__ q_start,
+    const FirstFitEntry* __restrict__ queue, PlaceSegs sg, uint32_t round, FirstFitState st,
+    int32_t* __restrict__ out_pod, int32_t* __restrict__ out_status, int32_t* __restrict__ out_pair,
+    int32_t* __restrict__ log) {
+  __shared__ PlaceMin mn;
+  __shared__ uint64_t head[2];
+  const int a = blockIdx.x, tid = threadIdx.x;
+  const int cur = st.cursor[a], end = q_start[a + 1];   // the cursor is this workgroup's own, round after round
+  if (cur >= end) return;
+  const int b = sg.seg_off[a], n = sg.seg_off[a + 1] - b;
+  if ((n <= PL_LDS_NODES) != IN_LDS) return;
+  int64_t* const g0 = sg.res + b;
+  const int64_t ss = sg.seg_stride;
+  const uint32_t* const gid = sg.gid + b;
+  if constexpr (IN_LDS) {
+    __shared__ PlaceShared sh;
+    const bool staged = first_fit_queue(
+        sh.r[0], sh.gid, std::integral_constant<int, PL_LDS_NODES>(), n, mn, head, groups, jobs, queue, cur, end, a, round,
+        st, out_pod, out_status, out_pair, log, [&]() {
+          for (int i = tid; i < n; i += PL_THREADS) {   // thread i mod PL_THREADS owns place i: no barrier
+#pragma unroll
+            for (int d = 0; d < D; ++d) sh.r[d][i] = g0[d * ss + i];
+            sh.lab[i] = gid[ss + i];
+            sh.gid[i] = gid[i];
+          }
+        });
+    if (staged)
+      for (int i = tid; i < n; i += PL_THREADS) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) g0[d * ss + i] = sh.r[d][i];
+      }
+  } else {
+    (void)first_fit_queue(g0, gid, ss, n, mn, head, groups, jobs, queue, cur, end, a, round, st, out_pod, out_status,
+                          out_pair, log, []() {});
+  }
+}
+
+__global__ __launch_bounds__(PM_THREADS) void first_fit_finish_kernel(PlaceSegs sg, int A, int64_t* __restrict__ res,
+                                                                     int64_t stride, uint32_t id_base) {
+  const int64_t i = (int64_t)blockIdx.x * PM_THREADS + threadIdx.x;
+  if (i >= sg.seg_off[A]) return;   // <= Ns places, every node in at most one segment
+  const int64_t l = (int64_t)(sg.gid[i] - id_base);   // < Ns: the fill kernel wrote id_base + local
+#pragma unroll
+  for (int d = 0; d < D; ++d) res[d * stride + l] = sg.res[d * sg.seg_stride + i];
+}
+
 }  // namespace
 
 hipError_t launch_place_members(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
@@ -276,6 +395,29 @@ hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const P
                      res, stride, (uint32_t)id_base, out_pod, out_status, log);
   hipLaunchKernelGGL(place_domains_kernel<false>, dim3((unsigned)A), dim3(PL_THREADS), 0, s, groups, jobs, job_start, segs,
                      res, stride, (uint32_t)id_base, out_pod, out_status, log);
+  return hipGetLastError();
+}
+
+hipError_t launch_first_fit_round(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* q_start,
+                                  const FirstFitEntry* queue, int A, const PlaceSegs& segs, int kinds, uint32_t round,
+                                  const FirstFitState& st, int32_t* out_pod, int32_t* out_status, int32_t* out_pair,
+                                  int32_t* log) {
+  if (A <= 0) return hipSuccess;
+  if (round == 0) return hipErrorInvalidValue;   // the zeroed words carry stamp 0
+  if (kinds & FF_SMALL)
+    hipLaunchKernelGGL(first_fit_round_kernel<true>, dim3((unsigned)A), dim3(PL_THREADS), 0, s, groups, jobs, q_start,
+                       queue, segs, round, st, out_pod, out_status, out_pair, log);
+  if (kinds & FF_LARGE)
+    hipLaunchKernelGGL(first_fit_round_kernel<false>, dim3((unsigned)A), dim3(PL_THREADS), 0, s, groups, jobs, q_start,
+                       queue, segs, round, st, out_pod, out_status, out_pair, log);
+  return hipGetLastError();
+}
+
+hipError_t launch_first_fit_finish(hipStream_t s, const PlaceSegs& segs, int A, int64_t Ns, int64_t* res, int64_t stride,
+                                   uint64_t id_base) {
+  const unsigned blocks = (unsigned)((Ns + PM_THREADS - 1) / PM_THREADS);
+  if (A <= 0 || blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(first_fit_finish_kernel, dim3(blocks), dim3(PM_THREADS), 0, s, segs, A, res, stride, (uint32_t)id_base);
   return hipGetLastError();
 }
 

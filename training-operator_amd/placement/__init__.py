@@ -601,6 +601,35 @@ class Engine:
                   "pe_gang_fit_domains")
         return GangFit(fits, fail, pods, fst)
 
+    def place_first_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
+                                pair_domain, level, level_size, parent=None, pairs=True):
+        """pe_place_first_fit_domains: every job, in (priority desc, index asc) order, is placed in the first of
+        its candidate domains -- its pairs in ascending p, as for gang_fit_domains -- in which place_greedy_domains
+        would place it against the residuals as the earlier jobs of the batch left them; a job whose candidates all
+        fail, or that is in no pair, is unschedulable.  Residuals are updated in place.  Returns (pod_node,
+        job_status, job_pair): job_pair[j] is the pair that placed job j or -1 (None with pairs=False)."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        pj = _c(pair_job, np.int32).reshape(-1)
+        pd = _c(pair_domain, np.int32).reshape(-1)
+        if pj.shape != pd.shape:
+            raise ValueError("pair_job and pair_domain must have one length")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        jp = np.full(max(J, 1), -1, dtype=np.int32) if pairs else None
+        self._chk(self.lib.pe_place_first_fit_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
+                                                      _p(nd), len(pj), _p(pj), _p(pd), int(level), len(ls), _p(ls),
+                                                      _p(par), _p(pod), _p(st), _p(jp)), "pe_place_first_fit_domains")
+        return pod[:P], st[:J], (jp[:J] if pairs else None)
+
     # ------------------------------------------------------------ misc
     def synchronize(self):
         self._chk(self.lib.pe_synchronize(self.h), "pe_synchronize")

@@ -93,6 +93,7 @@ SIGNATURES = {
     "pe_place_greedy": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P]),
     "pe_place_greedy_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, P, P]),
     "pe_gang_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
+    "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
