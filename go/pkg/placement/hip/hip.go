@@ -798,6 +798,50 @@ func (e *Engine) PlaceFirstFitDomains(g *Gangs, pairJob, pairDomain []int32, lev
 	return podNode, jobStatus, jobPair, e.err(rc, "pe_place_first_fit_domains")
 }
 
+// Victims are placed gangs in the shape the placement calls take and return: victim v has the groups
+// [GroupOff[v], GroupOff[v+1]) with GroupCount pods of GroupReq each ([VG][4], flattened), and PodNode holds the
+// global node id of every pod slot, groups in input order, -1 for a slot that was skipped.
+type Victims struct {
+	GroupOff   []int32
+	GroupCount []int32
+	GroupReq   []int64
+	PodNode    []int32
+}
+
+// MaxPairVictims is PE_MAX_PAIR_VICTIMS: the longest list of candidate victims of one pair.
+const MaxPairVictims = C.PE_MAX_PAIR_VICTIMS
+
+// GangPreemptDomains answers, for every pair p of GangFitDomains with the candidate victims
+// pairVic[pairVicOff[p]:pairVicOff[p+1]] in eviction order, which of them must go for job pairJob[p] to be placed
+// ALONE in the level-`level` domain pairDomain[p].  prefix[p] is the smallest prefix of the list whose release
+// places the job (0: it fits as things stand, -1: it never does); victims[p] is the set that remains after every
+// victim the job is placed without was put back, last candidate first (bit i = list position i); count[p] is its
+// size, or -1; best[j] is the pair of job j with the smallest count, ties to the smallest p, or -1.  Read-only: a
+// caller evicts, lets the Node informer's PE_NODE_SET bring the new residuals and then calls PlaceGreedyDomains.
+// selectionOnly leaves the three per-pair answers nil (they never cross).  A sharded engine refuses the call.
+func (e *Engine) GangPreemptDomains(g *Gangs, v *Victims, pairJob, pairDomain, pairVicOff, pairVic []int32, level int32, levelSize, parent []int32, selectionOnly bool) (prefix []int32, victims []uint64, count []int32, best []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	V := len(v.GroupOff) - 1
+	P := len(pairJob)
+	if len(pairDomain) != P {
+		return nil, nil, nil, nil, fmt.Errorf("GangPreemptDomains: %d jobs for %d domains", P, len(pairDomain))
+	}
+	if len(pairVicOff) != P+1 {
+		return nil, nil, nil, nil, fmt.Errorf("GangPreemptDomains: %d list offsets for %d pairs", len(pairVicOff), P)
+	}
+	best = make([]int32, J)
+	if !selectionOnly {
+		prefix = make([]int32, P)
+		victims = make([]uint64, P)
+		count = make([]int32, P)
+	}
+	rc := C.pe_gang_preempt_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.GroupCount), ptr64(g.GroupReq),
+		ptru32(g.GroupNeed), C.int64_t(V), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq), ptr32(v.PodNode),
+		C.int64_t(P), ptr32(pairJob), ptr32(pairDomain), ptr32(pairVicOff), ptr32(pairVic), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(prefix), ptru64(victims), ptr32(count), ptr32(best))
+	return prefix, victims, count, best, e.err(rc, "pe_gang_preempt_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

@@ -567,6 +567,68 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
                                const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                                int32_t* out_pod_node, int32_t* out_job_status, int32_t* out_job_pair /*[J] or NULL*/);
 
+/* (ABI 7, additive) Which gangs must go for a gang to fit: the question behind pe_gang_fit_domains' "no".  A
+ * high-priority job finds its racks full; which of the lower-priority gangs already placed there would have
+ * to be evicted for it to be placed in this rack, and which candidate rack needs the fewest evictions?  The
+ * procedure is Kueue's and the kube-scheduler's: remove candidates in order until the incoming workload fits,
+ * then put back those that were not needed.  NO reference function, as pe_gang_fit_domains.  Read-only.
+ * The incoming jobs, levels, level_size, parent, dom_level(n), pair_job, pair_domain and the judgement "would
+ * pe_place_greedy_domains, given this single job in this domain and no other job, return PE_JOB_PLACED" mean
+ * exactly what they mean in pe_gang_fit_domains.
+ * The victims are placed gangs in the shape the placement calls take and return: victim v has the groups
+ * [vic_group_off[v], vic_group_off[v + 1]) with vic_group_count and vic_group_req, and vic_pod_node holds the
+ * GLOBAL node id of every pod slot, groups in input order (a group of count c owns c slots), -1 = slot skipped.
+ * Pair p comes with its candidate victims in eviction order: pair_vic[pair_vic_off[p] .. pair_vic_off[p + 1]),
+ * K_p of them, each an index into the victims.
+ * The residuals a judgement sees are R(E), for a set E of positions of pair p's list: the CURRENT residuals of
+ * the domain's nodes, and for every position i in E every pod of victim pair_vic[pair_vic_off[p] + i] whose
+ * node n has dom_level(n) == pair_domain[p] gives its group's request back to n in all four dimensions.
+ * Victim pods on nodes outside the domain, on removed slots and slots holding -1 count nothing; an island
+ * group of a victim is its pods like any other.  That victims really hold what they claim is the caller's
+ * business: running pods live in `used`, not in the reset snapshot, so there is nothing to check it against.
+ * The greedy best-fit rule is not monotone in the residuals (a release can make an earlier group choose another
+ * node and a later group fail), so neither "release everything, then test" nor a bisection is exact; the
+ * prefixes are walked in order:
+ *   Phase 1   out_prefix[p] = the smallest k in [0, K_p] for which the job is placed against R({0 .. k-1}),
+ *             the prefixes tried in ascending order; -1 when there is none.  k = 0 is pe_gang_fit_domains'
+ *             out_fits[p].
+ *   Phase 2   (fill-back; only when out_prefix[p] = k >= 2)  E = {0 .. k-1}; for i = k-2 down to 0: if the job
+ *             is placed against R(E \ {i}) then E := E \ {i}.  Position k-1 is never tried.
+ *   out_victims[p] = E as a bit mask over the list positions (bit i = position i); 0 when the prefix is 0 or -1
+ *   out_count[p]   = the mask's popcount; -1 when the prefix is -1
+ *   out_best[j]    = the pair of job j with the smallest out_count >= 0, ties to the smallest p; -1 when there
+ *                    is none.  With empty lists it equals pe_gang_fit_domains' out_first.
+ * A pair costs at most (K_p + 1) + max(0, k - 1) judgements.  out_best is computed on the device; a caller who
+ * wants only the selection passes the three P-sized outputs NULL and they never cross.  Each out_* may be NULL;
+ * group_need NULL = 0.  n_pairs == 0, n_jobs == 0 and n_victims == 0 are PE_OK (no pairs: out_best all -1).
+ * A caller acts on the answer by evicting; the Node informer's PE_NODE_SET brings the new residuals, and
+ * pe_place_greedy_domains then places the gang.
+ * Read-only: the device residuals, the host mirror, the reset snapshot, the staged fit-mask state and pe_stats
+ * are left exactly as they are, and the call keeps nothing between calls.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): everything
+ * pe_gang_fit_domains refuses; about the victims' offsets, counts and requests everything pe_place_greedy
+ * refuses about a batch's; a NULL vic_pod_node when some victim group has pods; a vic_pod_node outside
+ * [-1, n_total); a NULL pair_vic_off with n_pairs > 0 or a pair_vic_off that does not rise from 0; a list
+ * longer than PE_MAX_PAIR_VICTIMS; a pair_vic outside [0, n_victims); the same victim twice in one pair's
+ * list (the same victim in many pairs is fine); and overflow: a node n that is not a removed slot and a
+ * dimension d for which the current residual plus the requests of ALL the call's victim pods on n exceeds
+ * INT64_MAX (so that no R(E) can overflow).  PE_ESTATE: a call before pe_load_nodes.  PE_ENOMEM: as
+ * pe_gang_fit_domains. */
+#define PE_MAX_PAIR_VICTIMS 64
+int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off /*[J+1]*/,
+                            const int32_t* group_count /*[G]*/, const int64_t* group_req /*[G][4]*/,
+                            const uint32_t* group_need /*[G] or NULL = 0*/,
+                            int64_t n_victims, const int32_t* vic_group_off /*[V+1]*/,
+                            const int32_t* vic_group_count /*[VG]*/, const int64_t* vic_group_req /*[VG][4]*/,
+                            const int32_t* vic_pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
+                            int64_t n_pairs, const int32_t* pair_job /*[P]*/, const int32_t* pair_domain /*[P]*/,
+                            const int32_t* pair_vic_off /*[P+1]*/, const int32_t* pair_vic /*victim indices*/,
+                            int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                            const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                            int32_t* out_prefix /*[P] or NULL*/, uint64_t* out_victims /*[P] or NULL*/,
+                            int32_t* out_count /*[P] or NULL*/, int32_t* out_best /*[J] or NULL*/);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

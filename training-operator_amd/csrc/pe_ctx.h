@@ -1,5 +1,5 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
+// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_preempt.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
 // the context itself.  Not part of the ABI.
 #pragma once
 
@@ -414,6 +414,21 @@ struct pe_ctx {
   HostBuf<uint8_t> ft_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
   DevBuf<uint8_t> ft_large;
   DevBuf<int64_t> ft_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
+  // which gangs must go for a gang to fit (pe_gang_preempt_domains, pe_engine_preempt.cpp).  As ft_*: every call
+  // sizes and fills what it uses, nothing of the hierarchy, the batch, the victims or the lists outlives a call.
+  HostBuf<uint8_t> pp_hin;      // one copy in: G PlaceGroup, P PrePair, U FitUnit, R PreRec, then the record CSR,
+  DevBuf<uint8_t> pp_in;        // the lists, leaf_dom and act_of
+  DevBuf<uint8_t> pp_out;       // one copy out: best [J] and the judgement counter (u64), then out_victims,
+  HostBuf<uint8_t> pp_hout;     // out_prefix and out_count [P] (16-B aligned)
+  DevBuf<int32_t> pp_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
+  DevBuf<int64_t> pp_seg;       // the segments' residuals [4][stride], read-only to the judging kernels
+  DevBuf<uint32_t> pp_segw;     // their global ids and labels, [2][stride]
+  DevBuf<int32_t> pp_place;     // node -> place in the segments' arrays [Ns], -1 = in no active domain
+  HostBuf<int32_t> pp_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
+  hipEvent_t pp_ev = nullptr;   // ... and the event behind that copy
+  HostBuf<uint8_t> pp_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
+  DevBuf<uint8_t> pp_large;
+  DevBuf<int64_t> pp_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
   // first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_engine_first_fit.cpp).
   // As pl_*: every call sizes and fills them anew.
   HostBuf<uint8_t> ff_hin;      // one copy in: G PlaceGroup, J PlaceJob (by job index), P FirstFitEntry, then
@@ -506,7 +521,10 @@ struct pe_ctx {
     ft_segw.release(); ft_hoff.release(); ft_hlarge.release(); ft_large.release(); ft_scratch.release();
     ff_hin.release(); ff_in.release(); ff_out.release(); ff_hout.release(); ff_log.release(); ff_dom.release();
     ff_seg.release(); ff_segw.release(); ff_state.release(); ff_hopen.release(); ff_hoff.release();
+    pp_hin.release(); pp_in.release(); pp_out.release(); pp_hout.release(); pp_dom.release(); pp_seg.release();
+    pp_segw.release(); pp_place.release(); pp_hoff.release(); pp_hlarge.release(); pp_large.release(); pp_scratch.release();
     if (ft_ev) (void)hipEventDestroy(ft_ev);
+    if (pp_ev) (void)hipEventDestroy(pp_ev);
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -586,7 +604,8 @@ inline void need_ptr(const void* p, const char* name) {
 // kernels; a successful call then leaves "S=<shapes> [P=<picks>] kernels_ms=<time>" (the capacity calls),
 // "A=<active domains> kernels_ms=<time>" (pe_place_greedy_domains), "A=<active domains> U=<units>
 // kernels_ms=<time>" (pe_gang_fit_domains) or "A=<active domains> rounds=<rounds launched> kernels_ms=<time>"
-// (pe_place_first_fit_domains) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
+// (pe_place_first_fit_domains) or "A=<active domains> U=<units> judged=<judgements> kernels_ms=<time>"
+// (pe_gang_preempt_domains) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
 // it on and off inside one process.
 struct CapEvents {
   pe_ctx* ctx;

@@ -57,11 +57,12 @@ struct FitPlan {
 
 // Builds the plan.  On any error `plan` is left exactly as it was, *bad_index (if given) receives the first
 // offending index (-1 where the error has none) and, for FIT_BAD_TREE, *tree_error the hierarchy's error.  A pair
-// is checked job first, then domain; the first offending pair is reported.
+// is checked job first, then domain; the first offending pair is reported.  unit_pairs: the places of a work unit,
+// FIT_UNIT_PAIRS for pe_gang_fit_domains; a caller whose pairs cost more each (pe_preempt_plan.h) cuts smaller ones.
 inline FitPlanError fit_plan_build(FitPlan& plan, int64_t n_jobs, int64_t n_pairs, const int32_t* pair_job,
                                    const int32_t* pair_domain, int32_t level, int32_t n_levels, const int32_t* level_size,
                                    const int32_t* parent, TreePlanError* tree_error = nullptr,
-                                   int64_t* bad_index = nullptr) {
+                                   int64_t* bad_index = nullptr, int unit_pairs = FIT_UNIT_PAIRS) {
   auto fail = [&](FitPlanError e, int64_t at) {
     if (bad_index) *bad_index = at;
     return e;
@@ -105,11 +106,11 @@ inline FitPlanError fit_plan_build(FitPlan& plan, int64_t n_jobs, int64_t n_pair
   std::vector<int32_t> fill(f.pair_start.begin(), f.pair_start.end() - 1);
   f.pairs.resize((size_t)n_pairs);
   for (int64_t p = 0; p < n_pairs; ++p) f.pairs[(size_t)fill[(size_t)f.act_of[(size_t)pair_domain[p]]]++] = (int32_t)p;
-  // the units: each domain's range cut into runs of FIT_UNIT_PAIRS, the last one shorter
+  // the units: each domain's range cut into runs of unit_pairs, the last one shorter
   f.unit_start.assign(A + 1, 0);
   for (size_t a = 0; a < A; ++a) {
-    for (int32_t p0 = f.pair_start[a]; p0 < f.pair_start[a + 1]; p0 += FIT_UNIT_PAIRS)
-      f.units.push_back(FitUnit{(int32_t)a, p0, std::min(p0 + FIT_UNIT_PAIRS, f.pair_start[a + 1]), 0});
+    for (int32_t p0 = f.pair_start[a]; p0 < f.pair_start[a + 1]; p0 += unit_pairs)
+      f.units.push_back(FitUnit{(int32_t)a, p0, std::min(p0 + unit_pairs, f.pair_start[a + 1]), 0});
     f.unit_start[a + 1] = (int32_t)f.units.size();
   }
   plan = std::move(f);

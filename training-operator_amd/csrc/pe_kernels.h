@@ -619,4 +619,45 @@ hipError_t launch_fit_large(hipStream_t s, const PlaceGroup* groups, const FitPa
                             const FitLarge* large, int64_t n_large, int64_t* scratch, const PlaceSegs& segs,
                             const FitOut& out);
 
+// ---- which gangs must go for a gang to fit (pe_gang_preempt_domains, pe_preempt.hip; the plan and its PreRec
+// records: pe_preempt_plan.h; units and FitLarge records as for the fit call).  The member lists are
+// launch_place_members', read-only here.
+struct PreRec;
+// One pair in plan order: its index in the caller's list, its job, the job's groups [g0, g1) and its candidate
+// victims list[v0 .. v1), at most 64.
+struct PrePair {
+  int32_t pair, job, g0, g1, v0, v1, pad_[2];
+};
+static_assert(sizeof(PrePair) == 32, "PrePair must be 32 B");
+// What the judging kernels read besides the segments.  node_place[Ns]: the place of local node n in the
+// segments' arrays, -1 = in no active domain (launch_preempt_place_map).
+struct PreIn {
+  const PlaceGroup* groups;
+  const PrePair* pairs;
+  const FitUnit* units;
+  const int32_t* list;        // victim indices, the pairs' lists back to back
+  const int32_t* rec_start;   // [V + 1]
+  const PreRec* recs;
+  const int32_t* node_place;
+  int64_t Ns;
+  uint64_t id_base;
+};
+// The answers of a call, on the device: best[J] (the caller sets every cell to ~0; unsigned minimum of
+// count << 32 | pair over the pairs with an answer), judged (one cell the caller zeroes: judgements made), and per
+// pair, by the caller's pair index, the mask, the prefix and the count.
+struct PreOut {
+  unsigned long long* best;
+  unsigned long long* judged;
+  uint64_t* victims;
+  int32_t* prefix;
+  int32_t* count;
+};
+// node_place[n] = s for every place s of the segments (the caller preset every cell to -1).
+hipError_t launch_preempt_place_map(hipStream_t s, const PlaceSegs& segs, int A, int64_t Ns, uint64_t id_base,
+                                    int32_t* node_place);
+// As launch_fit_units / launch_fit_large, for the two-phase walk of every pair.
+hipError_t launch_preempt_units(hipStream_t s, const PreIn& in, int64_t U, const PlaceSegs& segs, const PreOut& out);
+hipError_t launch_preempt_large(hipStream_t s, const PreIn& in, const FitLarge* large, int64_t n_large, int64_t* scratch,
+                                const PlaceSegs& segs, const PreOut& out);
+
 }  // namespace pe

@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -24,7 +24,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit"]
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS"]
 
 
 class PlacementError(RuntimeError):
@@ -116,6 +116,14 @@ class GangFit(NamedTuple):
     fail_group: Optional[np.ndarray]     # int32 [P]: -1, or the first group (within the job) not placed in full
     pods: Optional[np.ndarray]           # int64 [P]: pods the rule had placed when it stopped
     first: Optional[np.ndarray]          # int32 [J]: the smallest fitting pair of job j, -1 = none
+
+
+class GangPreempt(NamedTuple):
+    """Engine.gang_preempt_domains' answer; a part that was not asked for is None."""
+    prefix: Optional[np.ndarray]         # int32 [P]: the smallest prefix of the pair's list whose release places the job, -1 = none
+    victims: Optional[np.ndarray]        # uint64 [P]: the final set after the fill-back, bit i = position i of the list
+    count: Optional[np.ndarray]          # int32 [P]: its popcount, -1 when the prefix is -1
+    best: Optional[np.ndarray]           # int32 [J]: the pair of job j with the smallest count >= 0, ties to the smallest p; -1 = none
 
 
 def _level_sizes(level_size):
@@ -600,6 +608,50 @@ class Engine:
                                                len(ls), _p(ls), _p(par), _p(fits), _p(fail), _p(pods), _p(fst)),
                   "pe_gang_fit_domains")
         return GangFit(fits, fail, pods, fst)
+
+    def gang_preempt_domains(self, job_group_off, group_count, group_req, group_need, vic_group_off, vic_group_count,
+                             vic_group_req, vic_pod_node, pair_job, pair_domain, pair_vic_off, pair_vic, level, level_size,
+                             parent=None, tables=True, best=True) -> GangPreempt:
+        """pe_gang_preempt_domains: for every pair p, which of its candidate victims (pair_vic[pair_vic_off[p] ..
+        pair_vic_off[p + 1]), in eviction order) must go for job pair_job[p] to be placed ALONE in the level-`level`
+        domain pair_domain[p]?  Phase 1 finds the smallest prefix of the list whose release places the job, phase 2
+        puts back, from the end, every victim the job is placed without.  Read-only.  The incoming batch, the pairs
+        and the hierarchy are gang_fit_domains'; the victims are placed gangs: their groups (vic_group_off [V + 1],
+        vic_group_count, vic_group_req) and the global node id of every pod slot (vic_pod_node, -1 = skipped), as
+        the placement calls return them.  tables=False leaves the three [P] answers out (they never cross),
+        best=False the per-job pair with the fewest evictions."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        vgo = _c(vic_group_off, np.int32).reshape(-1)
+        V = len(vgo) - 1
+        vcnt = _c(vic_group_count, np.int32).reshape(-1)
+        vreq = _c(vic_group_req, np.int64).reshape(-1, 4)
+        vpn = None if vic_pod_node is None else _c(vic_pod_node, np.int32).reshape(-1)
+        pj = _c(pair_job, np.int32).reshape(-1)
+        pd = _c(pair_domain, np.int32).reshape(-1)
+        if pj.shape != pd.shape:
+            raise ValueError("pair_job and pair_domain must have one length")
+        pvo = _c(pair_vic_off, np.int32).reshape(-1)
+        if len(pvo) != len(pj) + 1:
+            raise ValueError("pair_vic_off must be [P + 1]")
+        pv = _c(pair_vic, np.int32).reshape(-1)
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = len(pj)
+        prefix = np.full(P, -1, dtype=np.int32) if tables else None
+        victims = np.zeros(P, dtype=np.uint64) if tables else None
+        count = np.full(P, -1, dtype=np.int32) if tables else None
+        bst = np.full(J, -1, dtype=np.int32) if best else None
+        self._chk(self.lib.pe_gang_preempt_domains(self.h, J, _p(jgo), _p(cnt), _p(req), _p(nd), V, _p(vgo), _p(vcnt),
+                                                   _p(vreq), _p(vpn), P, _p(pj), _p(pd), _p(pvo), _p(pv), int(level),
+                                                   len(ls), _p(ls), _p(par), _p(prefix), _p(victims), _p(count), _p(bst)),
+                  "pe_gang_preempt_domains")
+        return GangPreempt(prefix, victims, count, bst)
 
     def place_first_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
                                 pair_domain, level, level_size, parent=None, pairs=True):

@@ -27,6 +27,7 @@ PE_DIMS = 4
 PE_CAP_MAX = 2147483647
 PE_MAX_DOMAINS = 65536
 PE_MAX_LEVELS = 4
+PE_MAX_PAIR_VICTIMS = 64
 
 ERR_NAMES = {PE_EINVAL: "PE_EINVAL", PE_EOVERFLOW: "PE_EOVERFLOW", PE_ENOMEM: "PE_ENOMEM", PE_EHIP: "PE_EHIP",
              PE_ERCCL: "PE_ERCCL", PE_ESTATE: "PE_ESTATE", PE_ENODEV: "PE_ENODEV"}
@@ -94,6 +95,8 @@ SIGNATURES = {
     "pe_place_greedy_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, P, P]),
     "pe_gang_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
+    "pe_gang_preempt_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, P, P, i64, P, P, P, P, i32, i32, P, P,
+                                               P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
