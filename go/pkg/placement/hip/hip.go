@@ -707,6 +707,65 @@ func (e *Engine) GangCapacityTree(req []int64, need []uint32, count, maxLevel, l
 	return out, e.err(rc, "pe_gang_capacity_tree")
 }
 
+// TreeSplit is GangSplitTree's answer.
+type TreeSplit struct {
+	Level      []int32 // [J]: GangCapacityTree's level; -1 = none
+	Domain     []int32 // [J]: GangCapacityTree's domain; -1 = none
+	Parts      []int32 // [J]: number of (leaf, pods) parts; 0 = none selected, SplitTooMany
+	PartDomain []int32 // [J][maxParts]: the parts' leaf ids in list order, the tail -1
+	PartPods   []int32 // [J][maxParts]: their pods (>= 1, adding up to count), the tail 0
+	Spread     []int32 // [J][nLevels]: domains of each level the gang touches, 0 above the level
+}
+
+const (
+	// MaxSplitParts bounds GangSplitTree's maxParts.
+	MaxSplitParts = int32(C.PE_MAX_SPLIT_PARTS)
+	// SplitTooMany in Parts: the gang touches more than maxParts domains at some level.
+	SplitTooMany = int32(C.PE_SPLIT_TOO_MANY)
+)
+
+// GangSplitTree is GangCapacityTree's selection followed, on the device, by the descent from the selected
+// domain to the leaf level: at every level the children with the most slots first, so that the gang touches
+// the fewest domains, the remainder by best fit.  The parts of one job -- distinct leaves, pods adding up to
+// count[j], each within its leaf's slots -- go to PlaceGreedyDomains at level 0 as one job each and are all
+// placed.  count is required; maxLevel nil: the top level; levelSize and parent as for GangCapacityTree.  A
+// sharded engine refuses the call.  Read-only, like GangCapacity.
+func (e *Engine) GangSplitTree(req []int64, need []uint32, count, maxLevel, levelSize, parent []int32, maxParts int32) (*TreeSplit, error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, fmt.Errorf("GangSplitTree: %d needs for %d jobs", len(need), J)
+	}
+	if len(count) != J {
+		return nil, fmt.Errorf("GangSplitTree: %d counts for %d jobs", len(count), J)
+	}
+	if maxLevel != nil && len(maxLevel) != J {
+		return nil, fmt.Errorf("GangSplitTree: %d max levels for %d jobs", len(maxLevel), J)
+	}
+	L := len(levelSize)
+	valid := L >= 1 && L <= int(MaxLevels)
+	T := 0
+	for _, s := range levelSize {
+		valid = valid && s >= 1 && s <= MaxDomains
+		T += int(s)
+	}
+	if valid && parent != nil && len(parent) != T-int(levelSize[L-1]) {
+		return nil, fmt.Errorf("GangSplitTree: %d parents for %d columns below the top level", len(parent), T-int(levelSize[L-1]))
+	}
+	out := &TreeSplit{}
+	if valid && maxParts >= 1 && maxParts <= MaxSplitParts {
+		out.Level = make([]int32, J)
+		out.Domain = make([]int32, J)
+		out.Parts = make([]int32, J)
+		out.PartDomain = make([]int32, J*int(maxParts))
+		out.PartPods = make([]int32, J*int(maxParts))
+		out.Spread = make([]int32, J*L)
+	}
+	rc := C.pe_gang_split_tree(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(count), ptr32(maxLevel),
+		C.int32_t(L), ptr32(levelSize), ptr32(parent), C.int32_t(maxParts), ptr32(out.Level), ptr32(out.Domain),
+		ptr32(out.Parts), ptr32(out.PartDomain), ptr32(out.PartPods), ptr32(out.Spread))
+	return out, e.err(rc, "pe_gang_split_tree")
+}
+
 // Gangs is a greedy placement batch: jobs of groups of identical pods (include/placement.h).
 type Gangs struct {
 	JobGroupOff []int32  // [J+1]

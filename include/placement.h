@@ -429,6 +429,59 @@ int pe_gang_capacity_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][
                           int32_t* out_level /*[j] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
                           int64_t* out_domain_slots /*[j] or NULL*/, int32_t* out_feasible /*[j][n_levels] or NULL*/);
 
+/* (ABI 7, additive) A gang spread over the fewest domains: pe_gang_capacity_tree's selection, followed by the
+ * descent from the selected domain down to the leaf level -- the second phase of Kueue's topology-aware
+ * scheduling.  A gang that fits no rack but fits a block gets "these racks, with this many pods each", the
+ * fewest racks that hold it.  Levels, columns, level_size, parent, req, need, count, max_level and the table
+ * tree_slots[j][.] mean exactly what they mean in pe_gang_capacity_tree; slots(l, k) below is
+ * tree_slots[j][off_l + k] against the CURRENT residuals.
+ * Step 1, selection: out_level[j] and out_domain[j] are pe_gang_capacity_tree's, bit for bit: the lowest
+ * level <= max_level[j] with a domain of slots >= count[j], and there the best fit.  When there is none, both
+ * are -1, out_parts[j] is 0, out_spread[j][.] is 0 and the part rows are -1 (domains) and 0 (pods).
+ * Step 2, descent: S_L = [(out_domain[j], count[j])] with L = out_level[j].  For l = L down to 1 and for every
+ * (P, a) of S_l in list order: the children of P are the level-(l - 1) domains c with parent[off_{l-1} + c]
+ * == P (their slots add up to P's, so a <= slots(P) holds at every step).  Order them by (slots descending,
+ * id ascending) and walk them with r = a: while the current child's slots are < r it is a WHOLE part, gets all
+ * its slots, and r -= slots; at the first child with slots >= r the walk stops and the LAST part gets r pods.
+ * The last part goes to the child with the smallest slots >= r among those not yet taken, ties to the smallest
+ * id -- best fit for the remainder, so that large domains stay free for large gangs.  The parts are appended
+ * to S_{l-1}: the whole parts in walk order, then the last part.  S_0 is the answer, in list order:
+ *   out_part_domain[j][i] = a leaf id, out_part_pods[j][i] >= 1 for i < out_parts[j] = |S_0|; the unused
+ *                           tail of both rows ([max_parts] per job) is -1 / 0
+ *   out_spread[j][l]      = |S_l| for l <= L and 0 above: the domains of level l the gang touches.
+ *                           out_spread[j][L] = 1, out_spread[j][0] = out_parts[j]
+ * Consequences: the pods of a job's parts add up to count[j]; every part has pods <= slots(0, leaf); the
+ * leaves are distinct; per parent the number of children used is the smallest k for which the k largest
+ * children hold its allotment; a child without slots is never a part; with n_levels == 1 or out_level[j] == 0
+ * there is one part (out_domain[j], count[j]).
+ * max_parts in [1, PE_MAX_SPLIT_PARTS].  |S_l| never shrinks on the way down: a job whose |S_l| exceeds
+ * max_parts at ANY level has out_parts[j] = PE_SPLIT_TOO_MANY, part rows -1 / 0 and out_spread[j][.] 0, while
+ * out_level[j] and out_domain[j] stay valid.
+ * Acting on the answer: for need without PE_NEED_ISLAND give the parts of ONE job to pe_place_greedy_domains
+ * in one call, each part as a job of its own with one group (req, need, count = the part's pods), job_domain
+ * = the part's leaf, level 0.  All of them are placed: distinct leaves are disjoint nodes, and pods <= slots
+ * is exact by pe_gang_capacity's rule.  (Two jobs of one call may have been given the same free slots: place
+ * one, then ask again.)  With PE_NEED_ISLAND the bit is matched as a label bit, as in every capacity call.
+ * Read-only: residuals, host mirror, reset snapshot, staged fit-mask state and pe_stats are untouched, and
+ * nothing of the hierarchy is kept in the context.  Each out_* may be NULL; need NULL = 0, max_level NULL =
+ * n_levels - 1 for every job.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (the selection needs the global table; add the
+ * shards' tables and apply the rule on the host).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): everything
+ * pe_gang_capacity_tree refuses for a selection (count is required), and max_parts out of range.  PE_ESTATE:
+ * a call before pe_load_nodes.  An empty shard or n_jobs == 0 is PE_OK with -1 / 0 everywhere. */
+#define PE_MAX_SPLIT_PARTS 1024
+#define PE_SPLIT_TOO_MANY (-1)
+int pe_gang_split_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/,
+                       const uint32_t* need /* or NULL = 0 */, const int32_t* count /*[j], >= 1*/,
+                       const int32_t* max_level /*[j] or NULL = n_levels - 1*/,
+                       int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                       const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                       int32_t max_parts,
+                       int32_t* out_level /*[j] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
+                       int32_t* out_parts /*[j] or NULL*/, int32_t* out_part_domain /*[j][max_parts] or NULL*/,
+                       int32_t* out_part_pods /*[j][max_parts] or NULL*/, int32_t* out_spread /*[j][n_levels] or NULL*/);
+
 /* Greedy best-fit all-or-nothing gang placement.  Jobs in (priority
  * desc, index asc) order, groups of a job in the given order, pods of a group identical.
  *   job_group_off[J+1], priority[J], group_count[G] (pods to place), group_req[G][4],

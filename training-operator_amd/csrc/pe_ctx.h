@@ -387,6 +387,8 @@ struct pe_ctx {
   DevBuf<int32_t> lv_in;
   DevBuf<uint32_t> lv_out;      // one copy out: P TreeSel records, then the counts [P][n_levels]
   HostBuf<uint32_t> lv_hout;
+  DevBuf<int32_t> lv_split;     // pe_gang_split_tree: one slice of picks' parts (pe_split_plan.h SplitLayout), 64 MiB at most
+  HostBuf<int32_t> lv_hsplit;
   std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
   std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
   // gang placement inside a domain (pe_place_greedy_domains, pe_engine_place.cpp).  Every call sizes and fills
@@ -514,7 +516,7 @@ struct pe_ctx {
     aw_stage.release(); aw_outh.release(); aw_dev.release();
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
     lv_leaf.release(); lv_upper.release(); lv_hslots.release(); lv_hnodes.release();
-    lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release();
+    lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release(); lv_split.release(); lv_hsplit.release();
     pl_hin.release(); pl_in.release(); pl_out.release(); pl_hout.release(); pl_log.release(); pl_dom.release();
     pl_seg.release(); pl_segw.release();
     ft_hin.release(); ft_in.release(); ft_out.release(); ft_hout.release(); ft_dom.release(); ft_seg.release();

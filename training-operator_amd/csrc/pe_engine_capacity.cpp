@@ -1,17 +1,22 @@
 // libplacement: the gang-capacity calls -- pe_gang_capacity (the whole shard), pe_gang_capacity_domains
-// (per topology domain) and pe_gang_capacity_tree (over a hierarchy of levels).  All three reduce the batch
-// to its distinct pod shapes (cap_dedupe) and stage them the same way; the two table calls are one host
-// path, capacity_levels: a domain table is the tree of one level.  Own buffers (pe_ctx.h cp_*, lv_*):
+// (per topology domain) and pe_gang_capacity_tree (over a hierarchy of levels) -- and pe_gang_split_tree, the
+// tree call's selection followed by the descent that spreads the gang over the fewest domains.  All reduce the
+// batch to its distinct pod shapes (cap_dedupe) and stage them the same way; the table calls and the split are
+// one host path, capacity_levels: a domain table is the tree of one level.  Own buffers (pe_ctx.h cp_*, lv_*):
 // neither the residuals nor the staged fit-mask state are touched, and nothing is kept between calls.
 #include <type_traits>
 
 #include "pe_ctx.h"
 #include "pe_divmagic.h"
 #include "pe_first_seen.h"
+#include "pe_split_plan.h"
 #include "pe_tree_plan.h"
 
 static_assert(pe::TREE_MAX_LEVELS == PE_MAX_LEVELS && pe::TR_MAX_LEVELS == PE_MAX_LEVELS, "PE_MAX_LEVELS");
 static_assert(pe::TREE_MAX_LEVEL_SIZE == PE_MAX_DOMAINS, "PE_MAX_DOMAINS");
+static_assert(pe::SPLIT_MAX_PARTS == PE_MAX_SPLIT_PARTS && pe::SPLIT_TOO_MANY == PE_SPLIT_TOO_MANY &&
+                  pe::SPLIT_LEVELS == PE_MAX_LEVELS && pe::SPLIT_BUFFER_BYTES == (int64_t(64) << 20),
+              "pe_split_plan.h");
 static_assert(PE_MAX_LEVELS == 4, "a pick's key keeps max_level in 2 bits; the scatter of the counts names 1 .. 4");
 
 namespace {
@@ -88,6 +93,13 @@ struct LevelOut {
   int32_t* domain;         // [J]
   int64_t* domain_slots;   // [J]
   int32_t* feasible;       // [J][n_levels]
+  // pe_gang_split_tree alone (split: the call is one, whichever outputs it asked for)
+  bool split = false;
+  int32_t max_parts = 0;
+  int32_t* parts = nullptr;          // [J]
+  int32_t* part_domain = nullptr;    // [J][max_parts]
+  int32_t* part_pods = nullptr;      // [J][max_parts]
+  int32_t* spread = nullptr;         // [J][n_levels]
 };
 
 // Gang capacity over the levels of `plan`, for both table calls.  gang_capacity_domains_kernel adds every
@@ -98,10 +110,14 @@ struct LevelOut {
 // counts come back with one.  Both tables exist on the device for one chunk of shapes at a time (12 B per
 // shape and column, 64 MiB at most, 16 shapes at least); requested tables are copied out per chunk and
 // scattered to the jobs here, otherwise only the picks' answers cross.  max_level NULL: the top level.
+// A split call runs tree_split_kernel (pe_split.hip) behind the selection of every chunk, on slices of the
+// picks whose parts stay within 64 MiB on the device (pe_split_plan.h); a slice's answers come back with one
+// copy of the blocks the caller asked for and are scattered to the jobs at once.
 int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const int64_t* req, const uint32_t* need,
                     const int32_t* count, const int32_t* max_level, const LevelOut& out) {
   const int32_t n_levels = plan.n_levels;
-  const bool select = out.level || out.domain || out.domain_slots || out.feasible;
+  const bool select = out.split || out.level || out.domain || out.domain_slots || out.feasible;
+  const bool parts = out.parts || out.part_domain || out.part_pods || out.spread;
   const bool tables = out.slots || out.nodes;
   if (!cap_prologue(ctx, n_jobs, req, select, count)) return PE_OK;
   if (select && max_level) {
@@ -114,6 +130,10 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
     if (out.slots) std::memset(out.slots, 0, (size_t)(n_jobs * T) * sizeof(int64_t));
     if (out.nodes) std::memset(out.nodes, 0, (size_t)(n_jobs * T) * sizeof(int64_t));
     if (out.feasible) std::memset(out.feasible, 0, (size_t)(n_jobs * n_levels) * sizeof(int32_t));
+    if (out.parts) std::memset(out.parts, 0, (size_t)n_jobs * sizeof(int32_t));
+    if (out.spread) std::memset(out.spread, 0, (size_t)(n_jobs * n_levels) * sizeof(int32_t));
+    if (out.part_domain) std::fill_n(out.part_domain, n_jobs * out.max_parts, -1);
+    if (out.part_pods) std::memset(out.part_pods, 0, (size_t)(n_jobs * out.max_parts) * sizeof(int32_t));
     for (int64_t j = 0; j < n_jobs; ++j) {
       if (out.level) out.level[j] = -1;
       if (out.domain) out.domain[j] = -1;
@@ -174,6 +194,18 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
   }
   pe::TreeSel* const d_sel = (pe::TreeSel*)ctx->lv_out.p;
   uint32_t* const d_feas = ctx->lv_out.p + sel_words;
+  // the split's slices of picks: one device buffer and its pinned twin, sized for the largest slice
+  const int64_t slice = parts ? std::min<int64_t>(P, pe::split_slice_picks(out.max_parts)) : 0;
+  pe::SplitCsr csr{};
+  if (parts) {
+    const size_t w = (size_t)pe::SplitLayout{slice, out.max_parts}.words();
+    hipchk(ctx->lv_split.ensure(w), "alloc parts");
+    hipchk(ctx->lv_hsplit.ensure(w), "alloc pinned parts");
+    for (int l = 1; l < n_levels; ++l) {
+      csr.start_at[l] = plan.start_at[l];
+      csr.child_at[l] = plan.child_at[l];
+    }
+  }
   pe::TreeLevels lv{};
   lv.n_levels = n_levels;
   lv.pitch = (int32_t)U;
@@ -182,8 +214,10 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
     lv.col[l] = l == 0 ? 0 : plan.off[l] - plan.size[0];
   }
   ev.begin();
+  bool ev_open = true;   // kernels were launched since the events' end was last recorded
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int64_t sc = std::min(chunk, S - s0);
+    ev_open = true;
     // a table's slots and nodes are adjacent: one memset for the leaves (every cell of the upper table is
     // stored).  The node tables exist only for a caller who reads them (the selection reads the slots alone):
     // without them the leaf flush costs half the global atomics.
@@ -209,6 +243,32 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
     if (select)
       hipchk(pe::launch_tree_select(ctx->stream, d_slots, u_slots, s0, sc, lv, d_picks, P, d_sel, d_feas),
              "launch tree_select");
+    for (int64_t p0 = 0; parts && p0 < P; p0 += slice) {
+      const int64_t n = std::min(slice, P - p0);
+      // a pick is answered by the launch that holds its shape's rows
+      auto live = [&](int64_t p) {
+        const int64_t s = (int64_t)(keys[(size_t)p] >> 33) - s0;
+        return s >= 0 && s < sc;
+      };
+      if (sc < S && first_bad(n, [&](int64_t k) { return live(p0 + k); }) == n) continue;   // none of this chunk
+      const pe::SplitLayout sl{n, out.max_parts};
+      hipchk(pe::launch_tree_split(ctx->stream, d_slots, u_slots, s0, sc, lv, csr, d_plan, d_picks, d_sel, p0, n,
+                                   out.max_parts, ctx->lv_split.p),
+             "launch tree_split");
+      ev.end();   // before the slice's copy and scatter: with one slice the events span the kernels alone
+      ev_open = false;
+      const pe::SplitRange r = pe::split_copy_range(sl, out.part_domain, out.parts || out.spread, out.part_pods);
+      hipchk(hipMemcpyAsync(ctx->lv_hsplit.p + r.first, ctx->lv_split.p + r.first, (size_t)r.count * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, ctx->stream),
+             "D2H parts");
+      hipchk(hipStreamSynchronize(ctx->stream), "sync parts");
+      // rows of up to 8 KiB per job from picks all over the slice: a large batch is scattered by the planning pool
+      const int kT = n_jobs * pe::split_row_words(out.max_parts) >= (int64_t(1) << 20) ? 8 : 1;
+      plan_pool_run(kT, [&](int t) {
+        pe::split_scatter((const int32_t*)ctx->lv_hsplit.p, sl, p0, n_jobs * t / kT, n_jobs * (t + 1) / kT, pof.data(),
+                          n_levels, live, out.parts, out.part_domain, out.part_pods, out.spread);
+      });
+    }
     if (!tables) continue;
     // pinned copies: the chunk's leaf rows [sc][L0], then its upper rows [sc][U]
     if (out.slots) {
@@ -247,7 +307,7 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
       }
     }
   }
-  ev.end();
+  if (ev_open) ev.end();
   if (select)
     hipchk(hipMemcpyAsync(ctx->lv_hout.p, ctx->lv_out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
            "D2H selections");
@@ -368,6 +428,29 @@ int pe_gang_capacity_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const
     }
     return capacity_levels(ctx, plan, n_jobs, req, need, count, max_level,
                            LevelOut{out_tree_slots, out_tree_nodes, out_level, out_domain, out_domain_slots, out_feasible});
+  });
+}
+
+// The tree call's selection and, behind it on the same device tables, the descent to (leaf, pods) parts.
+int pe_gang_split_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, const int32_t* count,
+                       const int32_t* max_level, int32_t n_levels, const int32_t* level_size, const int32_t* parent,
+                       int32_t max_parts, int32_t* out_level, int32_t* out_domain, int32_t* out_parts,
+                       int32_t* out_part_domain, int32_t* out_part_pods, int32_t* out_spread) {
+  return guarded(ctx, [&]() -> int {
+    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    if (max_parts < 1 || max_parts > PE_MAX_SPLIT_PARTS) raise(PE_EINVAL, "max_parts outside [1, PE_MAX_SPLIT_PARTS]");
+    pe::TreePlan plan;
+    int64_t bad = -1;
+    const pe::TreePlanError te = pe::tree_plan_build(plan, n_levels, level_size, parent, &bad);
+    if (te != pe::TREE_OK) raise_tree(te, bad);
+    LevelOut out{nullptr, nullptr, out_level, out_domain, nullptr, nullptr};
+    out.split = true;
+    out.max_parts = max_parts;
+    out.parts = out_parts;
+    out.part_domain = out_part_domain;
+    out.part_pods = out_part_pods;
+    out.spread = out_spread;
+    return capacity_levels(ctx, plan, n_jobs, req, need, count, max_level, out);
   });
 }
 

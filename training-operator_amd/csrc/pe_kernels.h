@@ -513,6 +513,22 @@ hipError_t launch_tree_select(hipStream_t s, const uint64_t* leaf_slots, const u
                               int64_t S, const TreeLevels& levels, const TreePick* picks, int64_t P, TreeSel* out,
                               uint32_t* feasible);
 
+// ---- a gang spread over the fewest domains (pe_gang_split_tree, pe_split.hip; the arithmetic, the slice
+// buffer's layout and the scatter: pe_split_plan.h)
+// Where the CSR of level l >= 1 lies in the plan's words (pe_tree_plan.h start_at / child_at).
+struct SplitCsr {
+  int32_t start_at[TR_MAX_LEVELS];
+  int32_t child_at[TR_MAX_LEVELS];
+};
+// The descent for the picks [p0, p0 + n) whose shape lies in [s0, s0 + S), after launch_tree_select wrote
+// sel[p] for them from the same tables: their rows of the slice buffer buf (SplitLayout{n, max_parts}) get the
+// parts (domain and pods, the unused tail -1 / 0), the number of parts (0: none selected, SPLIT_TOO_MANY) and
+// the spread per level.  max_parts in [1, SPLIT_MAX_PARTS].
+hipError_t launch_tree_split(hipStream_t s, const uint64_t* leaf_slots, const uint64_t* upper_slots, int64_t s0,
+                             int64_t S, const TreeLevels& levels, const SplitCsr& csr, const int32_t* plan,
+                             const TreePick* picks, const TreeSel* sel, int64_t p0, int64_t n, int max_parts,
+                             int32_t* buf);
+
 // ---- gang placement inside a chosen domain (pe_place_greedy_domains, pe_place.hip; the plan: pe_place_plan.h)
 constexpr int PL_THREADS = 256;       // threads of a domain's workgroup
 // A domain's working state (four residuals, labels, node id: 40 B per node) lives in LDS up to this many

@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -24,7 +24,8 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS"]
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
+           "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY"]
 
 
 class PlacementError(RuntimeError):
@@ -110,6 +111,16 @@ class TreeCapacity(NamedTuple):
     feasible: Optional[np.ndarray]       # int32 [J][n_levels]: domains of each level with slots >= count
 
 
+class TreeSplit(NamedTuple):
+    """Engine.gang_split_tree's and split_tree's answer."""
+    level: np.ndarray                    # int32 [J]: gang_capacity_tree's level, -1 = none
+    domain: np.ndarray                   # int32 [J]: gang_capacity_tree's domain, -1 = none
+    parts: np.ndarray                    # int32 [J]: number of (leaf, pods) parts; 0 = none selected, PE_SPLIT_TOO_MANY
+    part_domain: np.ndarray              # int32 [J][max_parts]: the parts' leaf ids in list order, the tail -1
+    part_pods: np.ndarray                # int32 [J][max_parts]: their pods (>= 1, adding up to count), the tail 0
+    spread: np.ndarray                   # int32 [J][n_levels]: domains of each level the gang touches, 0 above the level
+
+
 class GangFit(NamedTuple):
     """Engine.gang_fit_domains' answer; a part that was not asked for is None."""
     fits: Optional[np.ndarray]           # uint8 [P]: 1 = the job alone would be placed in the domain right now
@@ -166,6 +177,71 @@ def select_tree(tree_slots, count, level_size, max_level=None):
         level[take], domain[take], slots[take] = l, d[take], s[take]
         off += int(ls[l])
     return level, domain, slots, feasible
+
+
+def _split_children(a, ids, slots):
+    """One parent's step of pe_gang_split_tree: allotment a over the children (ids ascending, their slots) ->
+    [(child, pods)], the whole parts in walk order, then the last part."""
+    order = sorted(range(len(ids)), key=lambda i: (-slots[i], ids[i]))
+    out, r = [], a
+    for pos, i in enumerate(order):
+        if slots[i] >= r:
+            last = min((x for x in order[pos:] if slots[x] >= r), key=lambda x: (slots[x], ids[x]))
+            return out + [(ids[last], r)]
+        out.append((ids[i], slots[i]))
+        r -= slots[i]
+    raise ValueError("tree_slots is not the roll-up of its children along parent")
+
+
+def split_tree(tree_slots, count, level_size, parent=None, max_level=None, max_parts=PE_MAX_SPLIT_PARTS) -> TreeSplit:
+    """The rule of pe_gang_split_tree on a host table: for the shards' tree_slots tables ADDED UP ([J][T]),
+    count [J] >= 1, the hierarchy (level_size, parent) the tables were made with and max_level [J] or None, the
+    selection of select_tree followed by the descent that spreads each gang over the fewest domains of every
+    level below.  max_parts in [1, PE_MAX_SPLIT_PARTS]; a job whose list passes it at any level has parts =
+    PE_SPLIT_TOO_MANY, rows -1 / 0 and spread 0."""
+    ls = _level_sizes(level_size)
+    L = len(ls)
+    if not 1 <= int(max_parts) <= PE_MAX_SPLIT_PARTS:
+        raise ValueError("max_parts must be in [1, PE_MAX_SPLIT_PARTS]")
+    mp = int(max_parts)
+    level, domain, _, _ = select_tree(tree_slots, count, ls, max_level)
+    t = np.asarray(tree_slots, dtype=np.int64)
+    cnt = np.asarray(count, dtype=np.int64).reshape(-1)
+    J = cnt.shape[0]
+    off = np.concatenate([[0], np.cumsum(ls)]).astype(np.int64)
+    par = np.zeros(0, dtype=np.int64) if parent is None else np.asarray(parent, dtype=np.int64).reshape(-1)
+    if len(par) != int(off[L] - ls[-1]):
+        raise ValueError("parent must be [sum(level_size) - level_size[-1]]")
+    kids = [None] + [[np.flatnonzero(par[off[l - 1]:off[l]] == p) for p in range(int(ls[l]))] for l in range(1, L)]
+    parts = np.zeros(J, dtype=np.int32)
+    part_domain = np.full((J, mp), -1, dtype=np.int32)
+    part_pods = np.zeros((J, mp), dtype=np.int32)
+    spread = np.zeros((J, L), dtype=np.int32)
+    for j in range(J):
+        if level[j] < 0:
+            continue
+        cur = [(int(domain[j]), int(cnt[j]))]
+        sp = [0] * L
+        sp[level[j]] = 1
+        for l in range(int(level[j]), 0, -1):
+            nxt = []
+            for p, a in cur:
+                ids = kids[l][p]
+                nxt += _split_children(a, ids.tolist(), t[j, off[l - 1] + ids].tolist())
+                if len(nxt) > mp:
+                    break
+            cur = nxt
+            sp[l - 1] = len(cur)
+            if len(cur) > mp:
+                break
+        if len(cur) > mp:
+            parts[j] = PE_SPLIT_TOO_MANY
+            continue
+        parts[j] = len(cur)
+        spread[j] = sp
+        part_domain[j, :len(cur)] = [c for c, _ in cur]
+        part_pods[j, :len(cur)] = [n for _, n in cur]
+    return TreeSplit(level, domain, parts, part_domain, part_pods, spread)
 
 
 def comm_id() -> bytes:
@@ -534,6 +610,47 @@ class Engine:
                                                  _p(domain_slots), _p(feasible)),
                   "pe_gang_capacity_tree")
         return TreeCapacity(tree_slots, tree_nodes, level, domain, domain_slots, feasible)
+
+    def gang_split_tree(self, req, need=None, count=None, max_level=None, level_size=None, parent=None,
+                        max_parts=64) -> TreeSplit:
+        """pe_gang_split_tree: gang_capacity_tree's selection (level, domain) followed, on the device, by the
+        descent that spreads each gang over the fewest domains of every level below the selected one.  Arguments
+        as gang_capacity_tree (count is required); max_parts in [1, PE_MAX_SPLIT_PARTS] is the width of the part
+        rows.  parts[j] (leaf, pods) pairs in part_domain[j] / part_pods[j], whose pods add up to count[j] on
+        distinct leaves; parts 0 = no level holds the gang, PE_SPLIT_TOO_MANY = more than max_parts domains at
+        some level.  On a sharded context add the shards' tree_slots and use split_tree.  Read-only."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        L = len(ls)
+        cnt = None if count is None else _c(count, np.int32)
+        if cnt is not None and cnt.shape != (J,):
+            raise ValueError("count must be [J]")
+        ml = None if max_level is None else _c(max_level, np.int32)
+        if ml is not None and ml.shape != (J,):
+            raise ValueError("max_level must be [J]")
+        valid = 1 <= L <= PE_MAX_LEVELS and bool(((ls >= 1) & (ls <= PE_MAX_DOMAINS)).all())
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        if valid and par is not None and len(par) != int(ls.astype(np.int64).sum()) - int(ls[-1]):
+            raise ValueError("parent must be [sum(level_size) - level_size[-1]]")
+        mp = int(max_parts)
+        w = mp if 1 <= mp <= PE_MAX_SPLIT_PARTS else 1   # (a max_parts the engine refuses allocates nothing here)
+        level = np.full(J, -1, dtype=np.int32)
+        domain = np.full(J, -1, dtype=np.int32)
+        parts = np.zeros(J, dtype=np.int32)
+        part_domain = np.full((J, w), -1, dtype=np.int32)
+        part_pods = np.zeros((J, w), dtype=np.int32)
+        spread = np.zeros((J, max(L, 1)), dtype=np.int32)
+        self._chk(self.lib.pe_gang_split_tree(self.h, J, _p(req), _p(nd), _p(cnt), _p(ml), L, _p(ls), _p(par), mp,
+                                              _p(level), _p(domain), _p(parts), _p(part_domain), _p(part_pods),
+                                              _p(spread)),
+                  "pe_gang_split_tree")
+        return TreeSplit(level, domain, parts, part_domain, part_pods, spread)
 
     # ------------------------------------------------------------ greedy
     def place_greedy(self, job_group_off, priority, group_count, group_req, group_need=None):

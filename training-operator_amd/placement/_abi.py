@@ -27,6 +27,8 @@ PE_DIMS = 4
 PE_CAP_MAX = 2147483647
 PE_MAX_DOMAINS = 65536
 PE_MAX_LEVELS = 4
+PE_MAX_SPLIT_PARTS = 1024
+PE_SPLIT_TOO_MANY = -1
 PE_MAX_PAIR_VICTIMS = 64
 
 ERR_NAMES = {PE_EINVAL: "PE_EINVAL", PE_EOVERFLOW: "PE_EOVERFLOW", PE_ENOMEM: "PE_ENOMEM", PE_EHIP: "PE_EHIP",
@@ -85,6 +87,7 @@ SIGNATURES = {
     "pe_gang_capacity": (ctypes.c_int, [P, i64, P, P, P, P, P]),
     "pe_gang_capacity_domains": (ctypes.c_int, [P, i64, P, P, P, i32, P, P, P, P, P]),
     "pe_gang_capacity_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, P, P, P, P, P, P]),
+    "pe_gang_split_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P]),
     "pe_jobs_upload": (ctypes.c_int, [P, i64, P, P]),
     "pe_fit_mask_run": (ctypes.c_int, [P]),
     "pe_fit_counts": (ctypes.c_int, [P, P]),
