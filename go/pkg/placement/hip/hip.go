@@ -901,6 +901,29 @@ func (e *Engine) GangPreemptDomains(g *Gangs, v *Victims, pairJob, pairDomain, p
 	return prefix, victims, count, best, e.err(rc, "pe_gang_preempt_domains")
 }
 
+// ReleaseGangs gives back what placed gangs hold (pe_release_gangs): every pod slot of v on a node that is not a
+// removed slot adds its group's request to the node's residuals; -1 slots count nothing, so the arguments and
+// outputs of a placement call -- an Unreserve, or the victims GangPreemptDomains names -- can be handed straight
+// back.  All-or-nothing: a call that would raise a residual above the reset snapshot fails and changes nothing.
+// Works on a sharded engine (every rank makes the same call).  pods is the number of pod slots that counted.
+func (e *Engine) ReleaseGangs(v *Victims) (pods int64, err error) {
+	var n C.int64_t
+	rc := C.pe_release_gangs(e.ctx, C.int64_t(len(v.GroupOff)-1), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq),
+		ptr32(v.PodNode), &n)
+	return int64(n), e.err(rc, "pe_release_gangs")
+}
+
+// AssumeGangs is the inverse (pe_assume_gangs): every counted pod slot takes its group's request off its node's
+// residuals -- the replay of the placements still in flight after LoadNodes or ResetResiduals.  It fails and
+// changes nothing when a residual would fall below 0; only these totals are checked, not labels, needs or the
+// best-fit rule.
+func (e *Engine) AssumeGangs(v *Victims) (pods int64, err error) {
+	var n C.int64_t
+	rc := C.pe_assume_gangs(e.ctx, C.int64_t(len(v.GroupOff)-1), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq),
+		ptr32(v.PodNode), &n)
+	return int64(n), e.err(rc, "pe_assume_gangs")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

@@ -682,6 +682,58 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                             int32_t* out_prefix /*[P] or NULL*/, uint64_t* out_victims /*[P] or NULL*/,
                             int32_t* out_count /*[P] or NULL*/, int32_t* out_best /*[J] or NULL*/);
 
+/* (ABI 7, additive) Give back and re-take placed gangs: the way back that the placement calls lack.  A gang
+ * scheduler's Unreserve (Permit timed out, a bind failed) returns one gang exactly; a caller replays the
+ * placements still in flight after pe_load_nodes or pe_reset_residuals; and the answer of
+ * pe_gang_preempt_domains can be carried out on the engine (release the victims, place the gang) without
+ * waiting for the Node informer.  NO reference function, as pe_place_greedy.
+ * The gangs are placed gangs in the shape the placement calls take and return, exactly pe_gang_preempt_domains'
+ * victims: gang v has the groups [gang_group_off[v], gang_group_off[v + 1]) with group_count and group_req,
+ * and pod_node holds the GLOBAL node id of every pod slot, groups in input order (a group of count c owns c
+ * slots), -1 = slot skipped.  The arguments and outputs of any placement call can be handed straight back.
+ * Rule: for every pod slot whose node n is >= 0 and not a removed slot, in all four dimensions d,
+ *   pe_release_gangs   res[n][d] += group_req[g][d]
+ *   pe_assume_gangs    res[n][d] -= group_req[g][d]
+ * Slots holding -1 and pods on removed slots count nothing (pe_gang_preempt_domains' R(E)), so the all -1 rows
+ * of an unschedulable job are harmless.  *out_pods (or NULL) = the pod slots that did count.
+ * All-or-nothing, validated in full before anything changes.  With sum[n][d] the call's total on node n, and
+ * only in the dimensions with sum[n][d] > 0 (a dimension the call does not move is not looked at: cap - used may
+ * legitimately be negative), products and sums formed in 128 bits so that nothing wraps:
+ *   release is refused unless res[n][d] + sum[n][d] <= the reset snapshot of n (cap - used as last loaded or set):
+ *           more is given back than was taken
+ *   assume  is refused unless res[n][d] - sum[n][d] >= 0: the pods do not fit
+ * A refusal is PE_EINVAL, pe_last_error names the offending node (the first at which the bound is crossed, in slot
+ * order), nothing is changed and out_pods is not written.  pe_assume_gangs checks these totals ONLY: labels,
+ * group needs and the best-fit rule are not consulted -- the caller vouches that the gangs sit where it says.
+ * Consequences:
+ *   - a placement call followed by pe_release_gangs of its own arguments and outputs leaves the residuals
+ *     bit-equal to those before it;
+ *   - pe_reset_residuals followed by pe_assume_gangs of the same placement gives the residuals the placement
+ *     call left;
+ *   - a release followed by an assume of the same gangs, or the other way round, is the identity;
+ *   - PE_NODE_SET of a node folds the placements on it into `used` and the reset snapshot: a later release of
+ *     them is refused, and the caller drops them.
+ * After the call the device residuals and the host mirror hold the new values; the reset snapshot, labels,
+ * islands, the staged fit batch and pe_stats are untouched, and the next pe_fit_mask_run, capacity call, what-if
+ * or placement (greedy walk or full scan) sees the new residuals.
+ * Sharded contexts: the calls work with world_size > 1.  Every rank makes the same call, as pe_update_nodes;
+ * every rank validates against its mirror of the global inventory, so all ranks decide alike without any
+ * exchange; every rank updates the whole mirror and, on the device, the nodes of its own shard.
+ * PE_EINVAL, nothing changed (the first offending index in pe_last_error where there is one): n_gangs < 0;
+ * everything pe_gang_preempt_domains refuses about its victims' offsets, counts and requests; a NULL pod_node
+ * when some group has pods; a pod_node outside [-1, n_total); the two refusals above.  PE_ESTATE: a call before
+ * pe_load_nodes.  n_gangs == 0 is PE_OK (*out_pods = 0).  PE_EHIP: as pe_place_greedy_domains, the mirror is not
+ * committed and the device residuals of the touched nodes are undefined until pe_reset_residuals or
+ * pe_load_nodes. */
+int pe_release_gangs(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off /*[V+1]*/,
+                     const int32_t* group_count /*[VG]*/, const int64_t* group_req /*[VG][4]*/,
+                     const int32_t* pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
+                     int64_t* out_pods /* or NULL */);
+int pe_assume_gangs(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off /*[V+1]*/,
+                    const int32_t* group_count /*[VG]*/, const int64_t* group_req /*[VG][4]*/,
+                    const int32_t* pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
+                    int64_t* out_pods /* or NULL */);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

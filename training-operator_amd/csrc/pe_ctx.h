@@ -1,5 +1,5 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_preempt.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
+// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_preempt.cpp, pe_engine_ledger.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
 // the context itself.  Not part of the ABI.
 #pragma once
 
@@ -26,6 +26,7 @@
 
 #include "pe_hostx.h"
 #include "pe_kernels.h"
+#include "pe_ledger_plan.h"
 #include "pe_resolver.h"
 #include "placement.h"
 
@@ -444,6 +445,12 @@ struct pe_ctx {
   DevBuf<uint64_t> ff_state;    // the rounds' state: the jobs' words [J], the unsettled count, the queue cursors [A]
   HostBuf<uint32_t> ff_hopen;   // the unsettled count read back
   HostBuf<int32_t> ff_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
+  // giving back and re-taking placed gangs (pe_release_gangs, pe_assume_gangs, pe_engine_ledger.cpp): the plan with
+  // its node -> scratch map (kept all -1 between calls, sized by the inventory) and the records of this shard's
+  // touched nodes on their way in.  Grow and are reused; nothing of the gangs outlives a call.
+  pe::LedgerPlan ld_plan;
+  HostBuf<pe::LedgerRec> ld_hin;
+  DevBuf<pe::LedgerRec> ld_in;
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -525,6 +532,7 @@ struct pe_ctx {
     ff_seg.release(); ff_segw.release(); ff_state.release(); ff_hopen.release(); ff_hoff.release();
     pp_hin.release(); pp_in.release(); pp_out.release(); pp_hout.release(); pp_dom.release(); pp_seg.release();
     pp_segw.release(); pp_place.release(); pp_hoff.release(); pp_hlarge.release(); pp_large.release(); pp_scratch.release();
+    ld_hin.release(); ld_in.release();
     if (ft_ev) (void)hipEventDestroy(ft_ev);
     if (pp_ev) (void)hipEventDestroy(pp_ev);
     for (hipEvent_t e : cp_ev)
@@ -607,7 +615,8 @@ inline void need_ptr(const void* p, const char* name) {
 // "A=<active domains> kernels_ms=<time>" (pe_place_greedy_domains), "A=<active domains> U=<units>
 // kernels_ms=<time>" (pe_gang_fit_domains) or "A=<active domains> rounds=<rounds launched> kernels_ms=<time>"
 // (pe_place_first_fit_domains) or "A=<active domains> U=<units> judged=<judgements> kernels_ms=<time>"
-// (pe_gang_preempt_domains) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
+// (pe_gang_preempt_domains) or "T=<records of this shard> steps=<steps> plan_us=<host plan time> kernels_ms=<time>"
+// (pe_release_gangs, pe_assume_gangs) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
 // it on and off inside one process.
 struct CapEvents {
   pe_ctx* ctx;

@@ -676,4 +676,18 @@ hipError_t launch_preempt_units(hipStream_t s, const PreIn& in, int64_t U, const
 hipError_t launch_preempt_large(hipStream_t s, const PreIn& in, const FitLarge* large, int64_t n_large, int64_t* scratch,
                                 const PlaceSegs& segs, const PreOut& out);
 
+// ---- giving back and re-taking placed gangs (pe_release_gangs, pe_assume_gangs, pe_ledger.hip)
+constexpr int LG_THREADS = 256;       // threads per block
+constexpr int LG_MAX_BLOCKS = 256;    // one block per CU; beyond LG_THREADS x LG_MAX_BLOCKS records the grid strides
+// One touched node of this shard: its local index and its four residuals after the call (absolute, the format
+// of launch_apply's updates).  The host computed them against its mirror; locals are unique within a launch.
+struct LedgerRec {
+  int64_t local;
+  int64_t res[D];
+};
+static_assert(sizeof(LedgerRec) == 40, "LedgerRec must be 40 B");
+// res[d][rec.local] = rec.res[d] for every record: plain stores, no read of the old value.  Every local must lie
+// in [0, stride).
+hipError_t launch_ledger_scatter(hipStream_t s, int64_t* res, int64_t stride, const LedgerRec* recs, int64_t n);
+
 }  // namespace pe

@@ -18,6 +18,7 @@
 #define PE_PREEMPT_PLAN_H_
 
 #include "pe_fit_plan.h"
+#include "pe_gang_slots.h"
 
 namespace pe {
 
@@ -49,6 +50,9 @@ enum PreemptPlanError {
   PRE_BAD_LIST_VICTIM = 15, // a pair_vic outside [0, n_victims); index = the position in pair_vic
   PRE_DUP_VICTIM = 16       // the same victim twice in one pair's list; index = the second position in pair_vic
 };
+static_assert(PRE_BAD_VICTIMS - GANGS_BAD_COUNT == PRE_BAD_POD_NODE - GANGS_BAD_POD_NODE &&
+                  PRE_NO_VIC_GROUPS - GANGS_NO_GROUPS == PRE_BAD_VICTIMS - GANGS_BAD_COUNT,
+              "the victims' errors are pe_gang_slots.h's, shifted");
 
 // One release record: node `node` gets q back.  sat (host only): bit d = q[d] is a saturated product.
 struct PreRec {
@@ -91,32 +95,12 @@ inline PreemptPlanError preempt_plan_build(PreemptPlan& plan, int64_t n_jobs, in
                                          parent, tree_error, &fbad, PRE_UNIT_PAIRS);
   if (fit_error) *fit_error = fe;
   if (fe != FIT_OK) return fail(PRE_BAD_FIT, fbad);
-  // ---- the victims
-  if (n_victims < 0 || n_victims > (int64_t)INT32_MAX) return fail(PRE_BAD_VICTIMS, -1);
+  // ---- the victims (pe_gang_slots.h: PRE_BAD_VICTIMS .. PRE_BAD_POD_NODE are its errors, in its order)
+  int64_t slots = 0, vbad = -1;
+  const GangSlotsError ve = gang_slots_check(n_victims, vic_group_off, vic_group_count, vic_group_req, vic_pod_node,
+                                             n_total, &slots, &vbad);
+  if (ve != GANGS_OK) return fail((PreemptPlanError)((int)ve + (PRE_BAD_VICTIMS - GANGS_BAD_COUNT)), vbad);
   const int64_t V = n_victims;
-  int64_t VG = 0;
-  if (V > 0) {
-    if (!vic_group_off) return fail(PRE_NO_VIC_OFF, -1);
-    if (vic_group_off[0] != 0) return fail(PRE_BAD_VIC_OFF, 0);
-    for (int64_t v = 0; v < V; ++v)
-      if (vic_group_off[v + 1] < vic_group_off[v]) return fail(PRE_BAD_VIC_OFF, v + 1);
-    VG = vic_group_off[V];
-  }
-  int64_t slots = 0;
-  if (VG > 0) {
-    if (!vic_group_count || !vic_group_req) return fail(PRE_NO_VIC_GROUPS, -1);
-    for (int64_t g = 0; g < VG; ++g) {
-      if (vic_group_count[g] < 0) return fail(PRE_BAD_VIC_COUNT, g);
-      for (int d = 0; d < 4; ++d)
-        if (vic_group_req[g * 4 + d] < 0) return fail(PRE_BAD_VIC_REQ, g);
-      slots += vic_group_count[g];
-    }
-  }
-  if (slots > 0) {
-    if (!vic_pod_node) return fail(PRE_NO_POD_NODE, -1);
-    for (int64_t s = 0; s < slots; ++s)
-      if (vic_pod_node[s] < -1 || vic_pod_node[s] >= n_total) return fail(PRE_BAD_POD_NODE, s);
-  }
   // ---- the lists
   const int64_t P = n_pairs;
   if (P > 0) {
@@ -143,13 +127,7 @@ inline PreemptPlanError preempt_plan_build(PreemptPlan& plan, int64_t n_jobs, in
   int64_t s = 0;
   for (int64_t v = 0; v < V; ++v) {
     for (int32_t g = vic_group_off[v]; g < vic_group_off[v + 1]; ++g) {
-      const int64_t e = s + vic_group_count[g];
-      while (s < e) {
-        const int32_t node = vic_pod_node[s];
-        int64_t run = 1;
-        while (s + run < e && vic_pod_node[s + run] == node) ++run;
-        s += run;
-        if (node < 0) continue;
+      const bool held = gang_group_runs(vic_pod_node, s, vic_group_count[g], [&](int32_t node, int64_t run) {
         PreRec r{};
         r.node = node;
         for (int d = 0; d < 4; ++d)
@@ -157,9 +135,11 @@ inline PreemptPlanError preempt_plan_build(PreemptPlan& plan, int64_t n_jobs, in
             r.q[d] = INT64_MAX;
             r.sat |= 1 << d;
           }
-        if (f.recs.size() >= (size_t)INT32_MAX) return fail(PRE_TOO_MANY, -1);
+        if (f.recs.size() >= (size_t)INT32_MAX) return false;
         f.recs.push_back(r);
-      }
+        return true;
+      });
+      if (!held) return fail(PRE_TOO_MANY, -1);
     }
     f.rec_start[(size_t)v + 1] = (int32_t)f.recs.size();
   }

@@ -770,6 +770,34 @@ class Engine:
                   "pe_gang_preempt_domains")
         return GangPreempt(prefix, victims, count, bst)
 
+    def _ledger(self, fn, what, gang_group_off, group_count, group_req, pod_node) -> int:
+        off = _c(gang_group_off, np.int32).reshape(-1)
+        cnt = _c(group_count, np.int32).reshape(-1)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        pod = None if pod_node is None else _c(pod_node, np.int32).reshape(-1)
+        if len(off) < 1 or len(cnt) != len(req):
+            raise ValueError("gang_group_off must be [V + 1], group_count and group_req one row per group")
+        if pod is not None and len(pod) < int(np.clip(cnt, 0, None).astype(np.int64).sum()):
+            raise ValueError("pod_node must hold one slot per pod")
+        pods = ctypes.c_int64(-1)
+        self._chk(fn(self.h, len(off) - 1, _p(off), _p(cnt), _p(req), _p(pod), ctypes.byref(pods)), what)
+        return pods.value
+
+    def release_gangs(self, gang_group_off, group_count, group_req, pod_node) -> int:
+        """pe_release_gangs: give back what placed gangs hold.  The gangs come in the shape the placement calls take
+        and return (gang_group_off [V + 1] -- a batch's job_group_off --, group_count, group_req, and pod_node = the
+        global node id of every pod slot, -1 = skipped): every pod slot on a node that is not a removed slot adds its
+        group's request to that node's residuals.  All-or-nothing: a call that would raise a residual above the reset
+        snapshot is PE_EINVAL and changes nothing.  Works on sharded contexts (every rank makes the same call).
+        Returns the number of pod slots that counted."""
+        return self._ledger(self.lib.pe_release_gangs, "pe_release_gangs", gang_group_off, group_count, group_req, pod_node)
+
+    def assume_gangs(self, gang_group_off, group_count, group_req, pod_node) -> int:
+        """pe_assume_gangs: the inverse of release_gangs -- every counted pod slot takes its group's request off its
+        node's residuals.  Refused (PE_EINVAL, nothing changed) when a residual would fall below 0; only these totals
+        are checked, not labels, needs or the best-fit rule.  Returns the number of pod slots that counted."""
+        return self._ledger(self.lib.pe_assume_gangs, "pe_assume_gangs", gang_group_off, group_count, group_req, pod_node)
+
     def place_first_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
                                 pair_domain, level, level_size, parent=None, pairs=True):
         """pe_place_first_fit_domains: every job, in (priority desc, index asc) order, is placed in the first of

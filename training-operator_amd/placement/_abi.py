@@ -100,6 +100,8 @@ SIGNATURES = {
     "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
     "pe_gang_preempt_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, P, P, i64, P, P, P, P, i32, i32, P, P,
                                                P, P, P, P]),
+    "pe_release_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
+    "pe_assume_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
