@@ -766,6 +766,66 @@ func (e *Engine) GangSplitTree(req []int64, need []uint32, count, maxLevel, leve
 	return out, e.err(rc, "pe_gang_split_tree")
 }
 
+// TreeSlices is GangSliceTree's answer: TreeSplit's, with the selected domain's units.
+type TreeSlices struct {
+	Level       []int32 // [J]: lowest level in [max(sliceLevel, 0), maxLevel] with a domain of units >= count / sliceSize; -1 = none
+	Domain      []int32 // [J]: that level's domain with the smallest such units, ties to the smallest id
+	DomainUnits []int64 // [J]: that domain's units (whole slices), 0 when none
+	Parts       []int32 // [J]: number of (leaf, pods) parts; 0 = none selected, SplitTooMany
+	PartDomain  []int32 // [J][maxParts]: the parts' leaf ids in list order, the tail -1
+	PartPods    []int32 // [J][maxParts]: their pods (>= 1, adding up to count), the tail 0
+	Spread      []int32 // [J][nLevels]: domains of each level the gang touches, 0 above the level
+}
+
+// SliceNode as a slice level: every slice inside one node.
+const SliceNode = int32(C.PE_SLICE_NODE)
+
+// GangSliceTree is GangSplitTree for gangs made of slices of sliceSize[j] pods (nil: 1) that must each sit
+// inside one domain of level sliceLevel[j] (nil: 0; SliceNode: inside one node) -- a tensor-parallel group per
+// node, per rack or per block.  Capacity counts whole slices at and above the slice level (a block's units are
+// the sum of its racks' units) and pods below it.  count[j] must be a multiple of sliceSize[j].  With
+// sliceLevel >= 0 the parts are placed as GangSplitTree's; with SliceNode part (leaf, a*z) is one job of a
+// groups {count z, need | NeedIsland} in that leaf.  A sharded engine refuses the call.  Read-only.
+func (e *Engine) GangSliceTree(req []int64, need []uint32, count, sliceSize, sliceLevel, maxLevel, levelSize, parent []int32, maxParts int32) (*TreeSlices, error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, fmt.Errorf("GangSliceTree: %d needs for %d jobs", len(need), J)
+	}
+	if len(count) != J {
+		return nil, fmt.Errorf("GangSliceTree: %d counts for %d jobs", len(count), J)
+	}
+	for _, a := range [][]int32{sliceSize, sliceLevel, maxLevel} {
+		if a != nil && len(a) != J {
+			return nil, fmt.Errorf("GangSliceTree: %d per-job values for %d jobs", len(a), J)
+		}
+	}
+	L := len(levelSize)
+	valid := L >= 1 && L <= int(MaxLevels)
+	T := 0
+	for _, s := range levelSize {
+		valid = valid && s >= 1 && s <= MaxDomains
+		T += int(s)
+	}
+	if valid && parent != nil && len(parent) != T-int(levelSize[L-1]) {
+		return nil, fmt.Errorf("GangSliceTree: %d parents for %d columns below the top level", len(parent), T-int(levelSize[L-1]))
+	}
+	out := &TreeSlices{}
+	if valid && maxParts >= 1 && maxParts <= MaxSplitParts {
+		out.Level = make([]int32, J)
+		out.Domain = make([]int32, J)
+		out.DomainUnits = make([]int64, J)
+		out.Parts = make([]int32, J)
+		out.PartDomain = make([]int32, J*int(maxParts))
+		out.PartPods = make([]int32, J*int(maxParts))
+		out.Spread = make([]int32, J*L)
+	}
+	rc := C.pe_gang_slice_tree(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(count), ptr32(sliceSize),
+		ptr32(sliceLevel), ptr32(maxLevel), C.int32_t(L), ptr32(levelSize), ptr32(parent), C.int32_t(maxParts),
+		ptr32(out.Level), ptr32(out.Domain), ptr64(out.DomainUnits), ptr32(out.Parts), ptr32(out.PartDomain),
+		ptr32(out.PartPods), ptr32(out.Spread))
+	return out, e.err(rc, "pe_gang_slice_tree")
+}
+
 // Gangs is a greedy placement batch: jobs of groups of identical pods (include/placement.h).
 type Gangs struct {
 	JobGroupOff []int32  // [J+1]

@@ -482,6 +482,59 @@ int pe_gang_split_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*
                        int32_t* out_parts /*[j] or NULL*/, int32_t* out_part_domain /*[j][max_parts] or NULL*/,
                        int32_t* out_part_pods /*[j][max_parts] or NULL*/, int32_t* out_spread /*[j][n_levels] or NULL*/);
 
+/* (ABI 7, additive) A gang in slices, each inside one domain: pe_gang_split_tree for a gang that is made of
+ * groups of z pods -- tensor- or pipeline-parallel groups -- which must each sit inside one scale-up domain
+ * (a node, a rack, a block) while the groups are free to spread: Kueue's podset slices (sliceSize,
+ * sliceRequiredTopology).  Capacity is counted in slices at and above the slice level and in pods below it.
+ * Unless stated otherwise levels, columns, level_size, parent, req, need, count, max_level, max_parts, cap(j, n)
+ * and slots(l, k), the -1 / 0 tails, PE_SPLIT_TOO_MANY, NULL outputs, read-only-ness, the empty shard and
+ * n_jobs == 0 mean exactly what they mean in pe_gang_split_tree.
+ * For job j write z = slice_size[j] (NULL = 1), sl = slice_level[j] (NULL = 0; PE_SLICE_NODE = every slice on
+ * one node), m = max(sl, 0) and u = count[j] / z, the slices wanted.
+ * Units: units(l, k) is defined for l >= m, against the CURRENT residuals.
+ *   sl == PE_SLICE_NODE: units(0, k) = sum over the nodes n of leaf domain k of floor(cap(j, n) / z)
+ *   sl >= 0:             units(sl, k) = floor(slots(sl, k) / z)
+ *   l > m:               units(l, p) = the sum of units(l - 1, c) over the children c of p -- NOT
+ *                        floor(slots(l, p) / z): two racks with 12 slots each hold 2 slices of 8, not 3.
+ * Selection: out_level[j] = the smallest l in [m, max_level[j]] at which some domain has units >= u;
+ * out_domain[j] = the domain of that level with the smallest such units, ties to the smallest id;
+ * out_domain_units[j] = that domain's units.  When there is none: -1, -1, 0, no parts, spread 0.
+ * Descent: S_L = [(out_domain[j], u)], in units.
+ *   1. For l = L down to m + 1: pe_gang_split_tree's step, word for word, with units(l - 1, .) in the place of
+ *      the slots.
+ *   2. At level m every entry (D, a) becomes (D, a * z), in pods.
+ *   3. For l = m down to 1: the same step with slots(l - 1, .).  a * z <= slots(m, D) because
+ *      a <= floor(slots(m, D) / z), so the step's premise is kept.
+ *   4. S_0 is the answer; out_spread[j][l] = |S_l|.  PE_SPLIT_TOO_MANY as soon as a list passes max_parts, with
+ *      out_level[j], out_domain[j] and out_domain_units[j] still valid.
+ * Consequences: the pods of a job's parts add up to count[j]; with sl <= 0 every part is a multiple of z; with
+ * sl >= 1 the pods that land under any one level-sl domain are a multiple of z; every part has pods <=
+ * slots(0, leaf); with sl == PE_SLICE_NODE every part's slices are <= units(0, leaf); the leaves are distinct;
+ * with z == 1 and sl in {PE_SLICE_NODE, 0} every output this call shares with pe_gang_split_tree is bit-equal
+ * to that call's.
+ * Acting on the answer.  sl >= 0: as pe_gang_split_tree, one one-group job per part at level 0.
+ * sl == PE_SLICE_NODE: part (leaf, a * z) goes to pe_place_greedy_domains as ONE job of a groups, each
+ * {count z, req, need | PE_NEED_ISLAND}, job_domain = leaf, level 0; the jobs of one answer in one call are all
+ * placed: an island group fits node n exactly when cap(j, n) >= z, and taking z pods lowers floor(cap / z) of
+ * that node by exactly one.  (Every node of a domain has an island, so the label bit matches.)
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): everything
+ * pe_gang_split_tree refuses, a slice_size below 1, a count that is not a multiple of its slice_size, a
+ * slice_level outside [PE_SLICE_NODE, n_levels), a max_level (given or defaulted) below max(slice_level, 0),
+ * world_size > 1 (node-level units cannot be had from the shards' tables).  PE_ESTATE: a call before
+ * pe_load_nodes. */
+#define PE_SLICE_NODE (-1)
+int pe_gang_slice_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/,
+                       const uint32_t* need /* or NULL = 0 */, const int32_t* count /*[j], >= 1*/,
+                       const int32_t* slice_size /*[j] or NULL = 1*/, const int32_t* slice_level /*[j] or NULL = 0*/,
+                       const int32_t* max_level /*[j] or NULL = n_levels - 1*/,
+                       int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                       const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                       int32_t max_parts,
+                       int32_t* out_level /*[j] or NULL*/, int32_t* out_domain /*[j] or NULL*/,
+                       int64_t* out_domain_units /*[j] or NULL*/,
+                       int32_t* out_parts /*[j] or NULL*/, int32_t* out_part_domain /*[j][max_parts] or NULL*/,
+                       int32_t* out_part_pods /*[j][max_parts] or NULL*/, int32_t* out_spread /*[j][n_levels] or NULL*/);
+
 /* Greedy best-fit all-or-nothing gang placement.  Jobs in (priority
  * desc, index asc) order, groups of a job in the given order, pods of a group identical.
  *   job_group_off[J+1], priority[J], group_count[G] (pods to place), group_req[G][4],

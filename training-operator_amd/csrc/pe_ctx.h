@@ -28,6 +28,7 @@
 #include "pe_kernels.h"
 #include "pe_ledger_plan.h"
 #include "pe_resolver.h"
+#include "pe_slice_plan.h"
 #include "placement.h"
 
 // (a namespace of their own: the inline functions below are visible outside the shared library, where
@@ -392,6 +393,7 @@ struct pe_ctx {
   HostBuf<int32_t> lv_hsplit;
   std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
   std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
+  pe::SlicePlan sl_plan;                   // pe_gang_slice_tree: the call's rows and picks (its buffers are cp_* and lv_*)
   // gang placement inside a domain (pe_place_greedy_domains, pe_engine_place.cpp).  Every call sizes and fills
   // what it uses, so calls of any shape may alternate with every other entry point; nothing of the hierarchy
   // or the batch outlives a call.  Grow and are reused.

@@ -2,13 +2,16 @@
 // (per topology domain) and pe_gang_capacity_tree (over a hierarchy of levels) -- and pe_gang_split_tree, the
 // tree call's selection followed by the descent that spreads the gang over the fewest domains.  All reduce the
 // batch to its distinct pod shapes (cap_dedupe) and stage them the same way; the table calls and the split are
-// one host path, capacity_levels: a domain table is the tree of one level.  Own buffers (pe_ctx.h cp_*, lv_*):
+// one host path, capacity_levels: a domain table is the tree of one level.  pe_gang_slice_tree, the split of a
+// gang in slices that each stay inside one domain, runs beside it (slice_levels) on tables with one row per
+// distinct (shape, slice size, slice level) and its own kernels (pe_slice.hip).  Own buffers (pe_ctx.h cp_*, lv_*):
 // neither the residuals nor the staged fit-mask state are touched, and nothing is kept between calls.
 #include <type_traits>
 
 #include "pe_ctx.h"
 #include "pe_divmagic.h"
 #include "pe_first_seen.h"
+#include "pe_slice_plan.h"
 #include "pe_split_plan.h"
 #include "pe_tree_plan.h"
 
@@ -17,6 +20,7 @@ static_assert(pe::TREE_MAX_LEVEL_SIZE == PE_MAX_DOMAINS, "PE_MAX_DOMAINS");
 static_assert(pe::SPLIT_MAX_PARTS == PE_MAX_SPLIT_PARTS && pe::SPLIT_TOO_MANY == PE_SPLIT_TOO_MANY &&
                   pe::SPLIT_LEVELS == PE_MAX_LEVELS && pe::SPLIT_BUFFER_BYTES == (int64_t(64) << 20),
               "pe_split_plan.h");
+static_assert(pe::SLICE_NODE == PE_SLICE_NODE, "pe_slice_plan.h");
 static_assert(PE_MAX_LEVELS == 4, "a pick's key keeps max_level in 2 bits; the scatter of the counts names 1 .. 4");
 
 namespace {
@@ -341,6 +345,187 @@ int capacity_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const
   return PE_OK;
 }
 
+// pe_gang_slice_tree: capacity_levels' path for a split, on tables with one row per distinct (shape, z, sl)
+// (pe_slice_plan.h) that hold slots below the level m = max(sl, 0) and units at and above it.  Per chunk of rows
+// (8 B per row and column, 64 MiB at most, 16 rows at least): slice_leaf_kernel fills the leaf rows -- node-level
+// rows in units --, slice_units_kernel turns the sl = 0 rows' leaves into units, tree_rollup_kernel folds level
+// after level as it does for every table call, slice_units_kernel again behind the roll-up of a level that some
+// row names; slice_select_kernel then answers the picks from their level m upward and slice_split_kernel
+// descends, in slices of picks as in capacity_levels.  The plan's words, the rows and the picks go in with one
+// copy; a slice's parts come back with one copy of the blocks asked for, the selections with one at the end.
+struct SliceOut {
+  int32_t max_parts;
+  int32_t* level;          // [J]
+  int32_t* domain;         // [J]
+  int64_t* domain_units;   // [J]
+  int32_t* parts;          // [J]
+  int32_t* part_domain;    // [J][max_parts]
+  int32_t* part_pods;      // [J][max_parts]
+  int32_t* spread;         // [J][n_levels]
+};
+int slice_levels(pe_ctx* ctx, const pe::TreePlan& plan, int64_t n_jobs, const int64_t* req, const uint32_t* need,
+                 const int32_t* count, const int32_t* slice_size, const int32_t* slice_level, const int32_t* max_level,
+                 const SliceOut& out) {
+  const int32_t n_levels = plan.n_levels;
+  const bool parts = out.parts || out.part_domain || out.part_pods || out.spread;
+  if (!cap_prologue(ctx, n_jobs, req, true, count)) return PE_OK;
+  if (max_level) {
+    const int64_t i =
+        first_bad(n_jobs, [max_level, n_levels](int64_t k) { return max_level[k] < 0 || max_level[k] >= n_levels; });
+    if (i < n_jobs) raise(PE_EINVAL, "max_level: value outside [0, n_levels) at index " + std::to_string(i));
+  }
+  int64_t bad = -1;
+  switch (pe::slice_validate(n_jobs, count, slice_size, slice_level, max_level, n_levels, &bad)) {
+    case pe::SLICE_OK: break;
+    case pe::SLICE_BAD_SIZE: raise(PE_EINVAL, "slice_size: value below 1 at index " + std::to_string(bad));
+    case pe::SLICE_BAD_COUNT: raise(PE_EINVAL, "count: not a multiple of slice_size at index " + std::to_string(bad));
+    case pe::SLICE_BAD_LEVEL:
+      raise(PE_EINVAL, "slice_level: value outside [PE_SLICE_NODE, n_levels) at index " + std::to_string(bad));
+    case pe::SLICE_BAD_MAX_LEVEL:
+      raise(PE_EINVAL, "max_level: value below max(slice_level, 0) at index " + std::to_string(bad));
+  }
+  if (ctx->Ns == 0) {   // an empty shard holds nothing
+    if (out.parts) std::memset(out.parts, 0, (size_t)n_jobs * sizeof(int32_t));
+    if (out.spread) std::memset(out.spread, 0, (size_t)(n_jobs * n_levels) * sizeof(int32_t));
+    if (out.part_domain) std::fill_n(out.part_domain, n_jobs * out.max_parts, -1);
+    if (out.part_pods) std::memset(out.part_pods, 0, (size_t)(n_jobs * out.max_parts) * sizeof(int32_t));
+    for (int64_t j = 0; j < n_jobs; ++j) {
+      if (out.level) out.level[j] = -1;
+      if (out.domain) out.domain[j] = -1;
+      if (out.domain_units) out.domain_units[j] = 0;
+    }
+    return PE_OK;
+  }
+  cap_dedupe(ctx, n_jobs, req, need);
+  pe::SlicePlan& sp = ctx->sl_plan;
+  pe::slice_plan_build(sp, n_jobs, ctx->cp_of.data(), count, slice_size, slice_level, max_level, n_levels);
+  const int64_t S = (int64_t)ctx->cp_uniq.size(), R = (int64_t)sp.rows.size(), P = (int64_t)sp.picks.size();
+  const int64_t T = plan.columns(), L0 = plan.size[0], U = plan.upper_columns();
+  CapEvents ev(ctx);
+  // the rows' shape records: a node-level row carries its z for the leaf kernel (pe_domains_body.h)
+  bool at_level[PE_MAX_LEVELS] = {false, false, false, false};   // levels whose rows need the conversion
+  hipchk(ctx->cp_hshapes.ensure((size_t)R), "alloc pinned shapes");
+  hipchk(ctx->cp_shapes.ensure((size_t)R), "alloc shapes");
+  for (int64_t r = 0; r < R; ++r) {
+    const pe::SliceRow& row = sp.rows[(size_t)r];
+    pe::CapShape rec = ctx->cp_uniq[row.shape];
+    rec.pad_[0] = row.sl == pe::SLICE_NODE ? (uint32_t)row.z : 0u;
+    std::memcpy((void*)(ctx->cp_hshapes.p + r), &rec, sizeof(rec));
+    if (row.sl >= 0 && row.z > 1) at_level[row.sl] = true;
+  }
+  hipchk(hipMemcpyAsync(ctx->cp_shapes.p, ctx->cp_hshapes.p, (size_t)R * sizeof(pe::CapShape), hipMemcpyHostToDevice,
+                        ctx->stream),
+         "H2D shapes");
+  const int64_t fit64 = (int64_t(64) << 20) / (8 * T);
+  const int64_t chunk = std::min<int64_t>(R, std::max<int64_t>(16, fit64));
+  hipchk(ctx->lv_leaf.ensure((size_t)(chunk * L0)), "alloc leaf tables");
+  if (U > 0) hipchk(ctx->lv_upper.ensure((size_t)(chunk * U)), "alloc upper tables");
+  // one pinned block and one copy in: the plan's words, then (16-B aligned) the rows, then the picks
+  static_assert(sizeof(pe::SliceRow) == 16 && sizeof(pe::TreePick) == 16, "16-B records");
+  const size_t words = plan.words.size(), row_at = (words + 3) / 4 * 4, pick_at = row_at + (size_t)R * 4;
+  const size_t in_words = pick_at + (size_t)P * 4;
+  hipchk(ctx->lv_hin.ensure(in_words), "alloc pinned plan, rows and picks");
+  hipchk(ctx->lv_in.ensure(in_words), "alloc plan, rows and picks");
+  if (words) std::memcpy((void*)ctx->lv_hin.p, plan.words.data(), words * sizeof(int32_t));
+  std::memcpy((void*)(ctx->lv_hin.p + row_at), sp.rows.data(), (size_t)R * sizeof(pe::SliceRow));
+  pe::TreePick* const h_picks = (pe::TreePick*)(ctx->lv_hin.p + pick_at);
+  for (int64_t p = 0; p < P; ++p) {
+    const uint64_t k = sp.picks[(size_t)p];
+    const uint32_t row = pe::slice_pick_row(k);
+    h_picks[p] = pe::TreePick{row, pe::slice_pick_units(k), pe::slice_pick_max_level(k), pe::slice_floor(sp.rows[row].sl)};
+  }
+  hipchk(hipMemcpyAsync(ctx->lv_in.p, ctx->lv_hin.p, in_words * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream),
+         "H2D plan, rows and picks");
+  const int32_t* const d_plan = ctx->lv_in.p;
+  const pe::SliceRow* const d_rows = (const pe::SliceRow*)(ctx->lv_in.p + row_at);
+  const pe::TreePick* const d_picks = (const pe::TreePick*)(ctx->lv_in.p + pick_at);
+  const size_t sel_words = (size_t)P * (sizeof(pe::TreeSel) / sizeof(uint32_t));
+  hipchk(ctx->lv_out.ensure(sel_words), "alloc selections");
+  hipchk(ctx->lv_hout.ensure(sel_words), "alloc pinned selections");
+  pe::TreeSel* const d_sel = (pe::TreeSel*)ctx->lv_out.p;
+  const int64_t slice = parts ? std::min<int64_t>(P, pe::split_slice_picks(out.max_parts)) : 0;
+  pe::SplitCsr csr{};
+  if (parts) {
+    const size_t w = (size_t)pe::SplitLayout{slice, out.max_parts}.words();
+    hipchk(ctx->lv_split.ensure(w), "alloc parts");
+    hipchk(ctx->lv_hsplit.ensure(w), "alloc pinned parts");
+    for (int l = 1; l < n_levels; ++l) {
+      csr.start_at[l] = plan.start_at[l];
+      csr.child_at[l] = plan.child_at[l];
+    }
+  }
+  pe::TreeLevels lv{};
+  lv.n_levels = n_levels;
+  lv.pitch = (int32_t)U;
+  for (int l = 0; l < n_levels; ++l) {
+    lv.size[l] = plan.size[l];
+    lv.col[l] = l == 0 ? 0 : plan.off[l] - plan.size[0];
+  }
+  ev.begin();
+  bool ev_open = true;   // kernels were launched since the events' end was last recorded
+  for (int64_t r0 = 0; r0 < R; r0 += chunk) {
+    const int64_t rc = std::min(chunk, R - r0);
+    ev_open = true;
+    uint64_t* const d_leaf = ctx->lv_leaf.p;
+    uint64_t* const d_upper = U > 0 ? ctx->lv_upper.p : nullptr;
+    hipchk(hipMemsetAsync(d_leaf, 0, (size_t)(rc * L0) * sizeof(uint64_t), ctx->stream), "zero leaf tables");
+    hipchk(pe::launch_slice_leaf(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
+                                 ctx->cp_shapes.p + r0, rc, (int)L0, d_leaf),
+           "launch slice_leaf");
+    if (at_level[0])
+      hipchk(pe::launch_slice_units(ctx->stream, d_leaf, L0, (int)L0, d_rows + r0, rc, 0), "launch slice_units");
+    for (int l = 1; l < n_levels; ++l) {   // level l from level l - 1
+      const bool leaf = l == 1;
+      hipchk(pe::launch_tree_rollup(ctx->stream, leaf ? d_leaf : d_upper + lv.col[l - 1], nullptr, leaf ? L0 : U,
+                                    d_plan + plan.start_at[l], d_plan + plan.child_at[l], plan.size[l], plan.width[l], rc,
+                                    d_upper + lv.col[l], nullptr, U),
+             "launch tree_rollup");
+      if (at_level[l])
+        hipchk(pe::launch_slice_units(ctx->stream, d_upper + lv.col[l], U, plan.size[l], d_rows + r0, rc, l),
+               "launch slice_units");
+    }
+    hipchk(pe::launch_slice_select(ctx->stream, d_leaf, d_upper, r0, rc, lv, d_picks, P, d_sel), "launch slice_select");
+    for (int64_t p0 = 0; parts && p0 < P; p0 += slice) {
+      const int64_t n = std::min(slice, P - p0);
+      // a pick is answered by the launch that holds its row
+      auto live = [&](int64_t p) {
+        const int64_t r = (int64_t)pe::slice_pick_row(sp.picks[(size_t)p]) - r0;
+        return r >= 0 && r < rc;
+      };
+      if (rc < R && first_bad(n, [&](int64_t k) { return live(p0 + k); }) == n) continue;   // none of this chunk
+      const pe::SplitLayout sl{n, out.max_parts};
+      hipchk(pe::launch_slice_split(ctx->stream, d_leaf, d_upper, r0, rc, lv, csr, d_plan, d_rows, d_picks, d_sel, p0, n,
+                                    out.max_parts, ctx->lv_split.p),
+             "launch slice_split");
+      ev.end();   // before the slice's copy and scatter: with one slice the events span the kernels alone
+      ev_open = false;
+      const pe::SplitRange rg = pe::split_copy_range(sl, out.part_domain, out.parts || out.spread, out.part_pods);
+      hipchk(hipMemcpyAsync(ctx->lv_hsplit.p + rg.first, ctx->lv_split.p + rg.first, (size_t)rg.count * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, ctx->stream),
+             "D2H parts");
+      hipchk(hipStreamSynchronize(ctx->stream), "sync parts");
+      const int kT = n_jobs * pe::split_row_words(out.max_parts) >= (int64_t(1) << 20) ? 8 : 1;
+      plan_pool_run(kT, [&](int t) {
+        pe::split_scatter((const int32_t*)ctx->lv_hsplit.p, sl, p0, n_jobs * t / kT, n_jobs * (t + 1) / kT,
+                          sp.pick_of.data(), n_levels, live, out.parts, out.part_domain, out.part_pods, out.spread);
+      });
+    }
+  }
+  if (ev_open) ev.end();
+  hipchk(hipMemcpyAsync(ctx->lv_hout.p, ctx->lv_out.p, sel_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
+         "D2H selections");
+  hipchk(hipStreamSynchronize(ctx->stream), "sync slice levels");
+  const pe::TreeSel* a = (const pe::TreeSel*)ctx->lv_hout.p;
+  for (int64_t j = 0; j < n_jobs; ++j) {
+    const pe::TreeSel& r = a[sp.pick_of[(size_t)j]];
+    if (out.level) out.level[j] = r.level;
+    if (out.domain) out.domain[j] = r.domain;
+    if (out.domain_units) out.domain_units[j] = (int64_t)r.slots;
+  }
+  ev.report_as("S=" + std::to_string(S) + " R=" + std::to_string(R) + " P=" + std::to_string(P));
+  return PE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -451,6 +636,25 @@ int pe_gang_split_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const ui
     out.part_pods = out_part_pods;
     out.spread = out_spread;
     return capacity_levels(ctx, plan, n_jobs, req, need, count, max_level, out);
+  });
+}
+
+// A gang in slices: the rows, the selection in units and the descent (slice_levels).
+int pe_gang_slice_tree(pe_ctx* ctx, int64_t n_jobs, const int64_t* req, const uint32_t* need, const int32_t* count,
+                       const int32_t* slice_size, const int32_t* slice_level, const int32_t* max_level, int32_t n_levels,
+                       const int32_t* level_size, const int32_t* parent, int32_t max_parts, int32_t* out_level,
+                       int32_t* out_domain, int64_t* out_domain_units, int32_t* out_parts, int32_t* out_part_domain,
+                       int32_t* out_part_pods, int32_t* out_spread) {
+  return guarded(ctx, [&]() -> int {
+    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    if (max_parts < 1 || max_parts > PE_MAX_SPLIT_PARTS) raise(PE_EINVAL, "max_parts outside [1, PE_MAX_SPLIT_PARTS]");
+    pe::TreePlan plan;
+    int64_t bad = -1;
+    const pe::TreePlanError te = pe::tree_plan_build(plan, n_levels, level_size, parent, &bad);
+    if (te != pe::TREE_OK) raise_tree(te, bad);
+    return slice_levels(ctx, plan, n_jobs, req, need, count, slice_size, slice_level, max_level,
+                        SliceOut{max_parts, out_level, out_domain, out_domain_units, out_parts, out_part_domain,
+                                 out_part_pods, out_spread});
   });
 }
 

@@ -529,6 +529,30 @@ hipError_t launch_tree_split(hipStream_t s, const uint64_t* leaf_slots, const ui
                              const TreePick* picks, const TreeSel* sel, int64_t p0, int64_t n, int max_parts,
                              int32_t* buf);
 
+// ---- a gang in slices, each inside one domain (pe_gang_slice_tree, pe_slice.hip; rows, picks and the unit
+// conversion: pe_slice_plan.h).  A call's tables have one row per distinct (shape, z, sl): slots below level
+// max(sl, 0), units at and above it.  A pick is a TreePick whose shape is the row, count the units wanted and
+// pad_ the lowest level max(sl, 0).
+struct SliceRow;
+// launch_gang_capacity_domains without the node table, for R rows: a record whose pad_[0] holds z >= 2 (a
+// node-level row) adds floor(cap / z) per node, a record with pad_[0] == 0 the node's capacity.
+hipError_t launch_slice_leaf(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
+                             const int32_t* island, int64_t Ns, const CapShape* shapes, int64_t R, int n_domains,
+                             uint64_t* dom_units);
+// table[r][k] = floor(table[r][k] / rows[r].z) for k < n_cols and every r < R with rows[r].sl == level: the
+// launch's rows of one level from slots to units, in place.  rows: the launch's first row.
+hipError_t launch_slice_units(hipStream_t s, uint64_t* table, int64_t pitch, int n_cols, const SliceRow* rows, int64_t R,
+                              int level);
+// launch_tree_select from the pick's lowest level upward, without the per-level counts.
+hipError_t launch_slice_select(hipStream_t s, const uint64_t* leaf_units, const uint64_t* upper_units, int64_t r0,
+                               int64_t R, const TreeLevels& levels, const TreePick* picks, int64_t P, TreeSel* out);
+// launch_tree_split with the lists turned from units to pods at the pick's lowest level.  rows: the call's
+// first row (a pick names its row by its number in the call).
+hipError_t launch_slice_split(hipStream_t s, const uint64_t* leaf_units, const uint64_t* upper_units, int64_t r0,
+                              int64_t R, const TreeLevels& levels, const SplitCsr& csr, const int32_t* plan,
+                              const SliceRow* rows, const TreePick* picks, const TreeSel* sel, int64_t p0, int64_t n,
+                              int max_parts, int32_t* buf);
+
 // ---- gang placement inside a chosen domain (pe_place_greedy_domains, pe_place.hip; the plan: pe_place_plan.h)
 constexpr int PL_THREADS = 256;       // threads of a domain's workgroup
 // A domain's working state (four residuals, labels, node id: 40 B per node) lives in LDS up to this many

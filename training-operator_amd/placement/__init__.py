@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -25,7 +25,7 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
-           "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY"]
+           "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE"]
 
 
 class PlacementError(RuntimeError):
@@ -115,6 +115,17 @@ class TreeSplit(NamedTuple):
     """Engine.gang_split_tree's and split_tree's answer."""
     level: np.ndarray                    # int32 [J]: gang_capacity_tree's level, -1 = none
     domain: np.ndarray                   # int32 [J]: gang_capacity_tree's domain, -1 = none
+    parts: np.ndarray                    # int32 [J]: number of (leaf, pods) parts; 0 = none selected, PE_SPLIT_TOO_MANY
+    part_domain: np.ndarray              # int32 [J][max_parts]: the parts' leaf ids in list order, the tail -1
+    part_pods: np.ndarray                # int32 [J][max_parts]: their pods (>= 1, adding up to count), the tail 0
+    spread: np.ndarray                   # int32 [J][n_levels]: domains of each level the gang touches, 0 above the level
+
+
+class TreeSlices(NamedTuple):
+    """Engine.gang_slice_tree's answer: TreeSplit's, with the selected domain's units."""
+    level: np.ndarray                    # int32 [J]: lowest level in [max(slice_level, 0), max_level] with a domain of units >= count / slice_size; -1 = none
+    domain: np.ndarray                   # int32 [J]: that level's domain with the smallest such units, ties to the smallest id
+    domain_units: np.ndarray             # int64 [J]: that domain's units (whole slices), 0 when none
     parts: np.ndarray                    # int32 [J]: number of (leaf, pods) parts; 0 = none selected, PE_SPLIT_TOO_MANY
     part_domain: np.ndarray              # int32 [J][max_parts]: the parts' leaf ids in list order, the tail -1
     part_pods: np.ndarray                # int32 [J][max_parts]: their pods (>= 1, adding up to count), the tail 0
@@ -651,6 +662,49 @@ class Engine:
                                               _p(spread)),
                   "pe_gang_split_tree")
         return TreeSplit(level, domain, parts, part_domain, part_pods, spread)
+
+    def gang_slice_tree(self, req, need=None, count=None, slice_size=None, slice_level=None, max_level=None,
+                        level_size=None, parent=None, max_parts=64) -> TreeSlices:
+        """pe_gang_slice_tree: gang_split_tree for gangs made of slices of slice_size[j] pods ([J] or None = 1) that
+        must each sit inside one domain of level slice_level[j] ([J] or None = 0; PE_SLICE_NODE = inside one node).
+        Capacity counts whole slices at and above the slice level -- a block's units are the sum of its racks'
+        units -- and pods below it; count[j] must be a multiple of slice_size[j] and max_level[j] at least
+        max(slice_level[j], 0).  With slice_level >= 0 the parts are placed as gang_split_tree's; with PE_SLICE_NODE
+        part (leaf, a * z) is one job of a groups {count z, need | PE_NEED_ISLAND} in that leaf.  A sharded context
+        refuses the call.  Read-only."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        L = len(ls)
+        per_job = {}
+        for name, v in (("count", count), ("slice_size", slice_size), ("slice_level", slice_level), ("max_level", max_level)):
+            per_job[name] = None if v is None else _c(v, np.int32)
+            if per_job[name] is not None and per_job[name].shape != (J,):
+                raise ValueError(name + " must be [J]")
+        valid = 1 <= L <= PE_MAX_LEVELS and bool(((ls >= 1) & (ls <= PE_MAX_DOMAINS)).all())
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        if valid and par is not None and len(par) != int(ls.astype(np.int64).sum()) - int(ls[-1]):
+            raise ValueError("parent must be [sum(level_size) - level_size[-1]]")
+        mp = int(max_parts)
+        w = mp if 1 <= mp <= PE_MAX_SPLIT_PARTS else 1   # (a max_parts the engine refuses allocates nothing here)
+        level = np.full(J, -1, dtype=np.int32)
+        domain = np.full(J, -1, dtype=np.int32)
+        units = np.zeros(J, dtype=np.int64)
+        parts = np.zeros(J, dtype=np.int32)
+        part_domain = np.full((J, w), -1, dtype=np.int32)
+        part_pods = np.zeros((J, w), dtype=np.int32)
+        spread = np.zeros((J, max(L, 1)), dtype=np.int32)
+        self._chk(self.lib.pe_gang_slice_tree(self.h, J, _p(req), _p(nd), _p(per_job["count"]), _p(per_job["slice_size"]),
+                                              _p(per_job["slice_level"]), _p(per_job["max_level"]), L, _p(ls), _p(par), mp,
+                                              _p(level), _p(domain), _p(units), _p(parts), _p(part_domain), _p(part_pods),
+                                              _p(spread)),
+                  "pe_gang_slice_tree")
+        return TreeSlices(level, domain, units, parts, part_domain, part_pods, spread)
 
     # ------------------------------------------------------------ greedy
     def place_greedy(self, job_group_off, priority, group_count, group_req, group_need=None):

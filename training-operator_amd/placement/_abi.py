@@ -29,6 +29,7 @@ PE_MAX_DOMAINS = 65536
 PE_MAX_LEVELS = 4
 PE_MAX_SPLIT_PARTS = 1024
 PE_SPLIT_TOO_MANY = -1
+PE_SLICE_NODE = -1
 PE_MAX_PAIR_VICTIMS = 64
 
 ERR_NAMES = {PE_EINVAL: "PE_EINVAL", PE_EOVERFLOW: "PE_EOVERFLOW", PE_ENOMEM: "PE_ENOMEM", PE_EHIP: "PE_EHIP",
@@ -88,6 +89,7 @@ SIGNATURES = {
     "pe_gang_capacity_domains": (ctypes.c_int, [P, i64, P, P, P, i32, P, P, P, P, P]),
     "pe_gang_capacity_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, P, P, P, P, P, P]),
     "pe_gang_split_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P]),
+    "pe_gang_slice_tree": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P, P]),
     "pe_jobs_upload": (ctypes.c_int, [P, i64, P, P]),
     "pe_fit_mask_run": (ctypes.c_int, [P]),
     "pe_fit_counts": (ctypes.c_int, [P, P]),
