@@ -871,6 +871,34 @@ func (e *Engine) PlaceGreedyDomains(g *Gangs, jobDomain []int32, level int32, le
 	return podNode, jobStatus, e.err(rc, "pe_place_greedy_domains")
 }
 
+// MinMemberAll as a minMember: the whole job is mandatory (PE_MIN_MEMBER_ALL).
+const MinMemberAll = int32(C.PE_MIN_MEMBER_ALL)
+
+// PlaceMinMemberDomains is PlaceGreedyDomains for gangs that are schedulable at minMember[j] pods (the PodGroup's
+// MinMember; nil or MinMemberAll: the whole job).  The mandatory pods -- the job's first minMember pod slots,
+// plus the rest of an island group the cut falls in -- are placed all-or-nothing; after that every group's
+// optional pods are placed as far as they fit, and the rest of the group keeps -1 and stays pending.  groupPods[g]
+// and jobPods[j] count the pods that hold a node; podNode and groupPods can be handed straight to ReleaseGangs /
+// AssumeGangs.  Residuals are updated in place.  A sharded engine refuses the call.
+func (e *Engine) PlaceMinMemberDomains(g *Gangs, minMember, jobDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus, groupPods []int32, jobPods []int64, err error) {
+	J := len(g.JobGroupOff) - 1
+	if minMember != nil && len(minMember) != J {
+		return nil, nil, nil, nil, fmt.Errorf("PlaceMinMemberDomains: %d min members for %d jobs", len(minMember), J)
+	}
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, nil, nil, fmt.Errorf("PlaceMinMemberDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	groupPods = make([]int32, len(g.GroupCount))
+	jobPods = make([]int64, J)
+	rc := C.pe_place_min_member_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), ptr32(minMember), ptr32(jobDomain), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus), ptr32(groupPods),
+		ptr64(jobPods))
+	return podNode, jobStatus, groupPods, jobPods, e.err(rc, "pe_place_min_member_domains")
+}
+
 // GangFitDomains answers, for every pair p, whether PlaceGreedyDomains would place job pairJob[p] ALONE in the
 // level-`level` domain pairDomain[p] against the current residuals (Gangs.Priority is not read).  Read-only.
 // fits[p] is 1 or 0, failGroup[p] -1 or the job's first group that was not placed in full, pods[p] the pods

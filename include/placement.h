@@ -586,6 +586,61 @@ int pe_place_greedy_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                             const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                             int32_t* out_pod_node, int32_t* out_job_status);
 
+/* (ABI 7, additive) MinMember first, the rest as fits: pe_place_greedy_domains for a PodGroup whose MinMember
+ * is below its pod total (an elastic PyTorchJob, any job with SchedulingPolicy.MinAvailable).  The gang is
+ * schedulable once min_member[j] pods hold a node; the other pods are bound as far as they fit and stay pending
+ * otherwise -- what Volcano and the coscheduling plugin do with the PodGroup.  The smallest case: a rack of two
+ * nodes with 8 free GPUs each, Master = 1 pod x 2 GPUs followed by Workers = 6 pods x 3 GPUs: 7 pods, 20 GPUs
+ * against 16 free, so pe_place_greedy_domains places nothing.  With min_member 4 the master and three workers
+ * are mandatory; the node that took the master holds two workers (6 / 3), the other node two (8 / 3): the job
+ * is placed with 5 pods, out_group_pods {1, 4}, the last two worker slots -1, and 0 and 2 GPUs left.  With
+ * min_member 6 the job is unschedulable and the residuals are untouched.
+ * NO reference function, as pe_place_greedy_domains.  Everything not said here means what it means in that
+ * call: jobs in (priority desc, index asc) order, groups in the given order, each pod on the argmin-key node of
+ * job_domain[j] at `level`, PE_NEED_ISLAND groups as one unit of count x request on one node (a product that
+ * overflows fits nowhere), zero-count groups skipped, pod slots in group input order with GLOBAL node ids.
+ * Totals and the mandatory share.  T_j is job j's pod total, b_g the pods of the job's groups before group g.
+ *   M_j = T_j when min_member is NULL or min_member[j] == PE_MIN_MEMBER_ALL, else min_member[j]
+ *   m_g = clamp(M_j - b_g, 0, count_g)    the mandatory pods of group g; an island group is indivisible:
+ *                                         m_g > 0 makes it count_g
+ *   o_g = count_g - m_g                   its optional pods
+ * So the mandatory pods are pod slots [0, M_j) of the job, plus the rest of an island group that M_j cuts.  With
+ * the groups given in CalcPGMinResources order these are the pods that aggregation mode V1 counts ("until
+ * podCnt == minMember"): MinResources of the PodGroup is the request of exactly the mandatory pods.
+ * Phase 1 (mandatory) is pe_place_greedy_domains' treatment of the job with the counts m_g: all-or-nothing,
+ * rolled back in full on the first pod that finds no node.  On failure the job is PE_JOB_UNSCHEDULABLE, every
+ * one of its pod slots is -1 (the optional ones too), its out_group_pods and out_job_pods are 0, the residuals
+ * are as before the job, and phase 2 is not tried.
+ * Phase 2 (optional), only after a placed phase 1, runs over the job's groups in order with o_g > 0.  A group
+ * without PE_NEED_ISLAND places its optional pods one at a time by the same argmin rule until a pod finds no
+ * node; the remaining slots of THAT group are -1 and the rule goes on with the next group.  An optional island
+ * group is placed as its one unit or not at all.  Nothing of phase 2 is rolled back; the job is PE_JOB_PLACED.
+ * Within a group the slots that hold a node are a prefix of its slots: mandatory first, then optional.
+ *   out_group_pods[g] = the pods of group g that hold a node
+ *   out_job_pods[j]   = their sum over the job's groups
+ * Every pod slot and every status is written; out_group_pods and out_job_pods may be NULL.  A job without groups
+ * or pods is placed.  A domain without nodes: a job with M_j == 0 is placed with 0 pods, a job with a mandatory
+ * pod is unschedulable.  n_jobs == 0 is PE_OK.
+ * Identities: with min_member NULL, or M_j == T_j for every job, out_pod_node, out_job_status and the residuals
+ * equal pe_place_greedy_domains'.  The outputs can be handed straight to pe_release_gangs / pe_assume_gangs
+ * (slots holding -1 count nothing).
+ * After the call the device residuals and the host mirror both hold the new residuals; pe_reset_residuals
+ * restores as usual and the staged fit batch stays valid.  pe_stats: adds to pods_placed (pods that hold a
+ * node), jobs_placed and jobs_failed only.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there
+ * is one): everything pe_place_greedy_domains refuses, a min_member[j] below -1 and a min_member[j] above T_j.
+ * PE_ESTATE: a call before pe_load_nodes. */
+#define PE_MIN_MEMBER_ALL (-1)
+int pe_place_min_member_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                                const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                                const int32_t* min_member /*[J], or NULL = every job PE_MIN_MEMBER_ALL*/,
+                                const int32_t* job_domain /*[J]*/, int32_t level,
+                                int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                                const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                                int32_t* out_pod_node, int32_t* out_job_status,
+                                int32_t* out_group_pods /*[G] or NULL*/, int64_t* out_job_pods /*[J] or NULL*/);
+
 /* (ABI 7, additive) Exact what-if of a whole gang per domain: would this job, all its groups in order, be
  * placed in this domain right now?  The read-only link between pe_gang_capacity_tree (which domains hold a
  * gang of ONE shape) and pe_place_greedy_domains (which places the gang and changes the residuals).  For a

@@ -598,6 +598,34 @@ hipError_t launch_place_domains(hipStream_t s, const PlaceGroup* groups, const P
                                 int A, const PlaceSegs& segs, int64_t* res, int64_t stride, uint64_t id_base,
                                 int32_t* out_pod, int32_t* out_status, int32_t* log);
 
+// ---- MinMember first, the rest as fits (pe_place_min_member_domains, pe_place_min.hip; the plan:
+// pe_place_min_plan.h).  Group g comes as one PlaceGroup -- its MANDATORY share: count = its mandatory pods, pod0 =
+// its first mandatory slot in the mandatory numbering -- and one PlaceMinOpt, its OPTIONAL share.
+struct PlaceMinOpt {
+  int64_t pod0;    // its first optional slot among all slots
+  int32_t count;   // its optional pods
+  int32_t pad_;
+};
+static_assert(sizeof(PlaceMinOpt) == 16, "PlaceMinOpt must be 16 B");
+// One job, in plan order: its index in the caller's batch, its groups [g0, g1), its mandatory records [g0, gm),
+// `shift` from a mandatory slot to the slot among all slots, and its pod total.  32 B, so that no record straddles
+// a 64-B line, and the shift itself rather than something to derive it from: the workgroup reads one record per
+// job with nothing else to do meanwhile (DESIGN.md section 24 has the measurements).
+struct PlaceMinJob {
+  int32_t job, g0, gm, g1;
+  int64_t shift, pods;
+};
+static_assert(sizeof(PlaceMinJob) == 32, "PlaceMinJob must be 32 B");
+// One workgroup per active domain a < A: its jobs in that order; phase 1 is launch_place_domains' all-or-nothing
+// loop over the mandatory records, phase 2 places the optional shares as far as they fit and rolls nothing back.
+// out_pod [P] (every slot of every job is written), out_group_pods [G] (zeroed by the caller; a placed job writes
+// every one of its groups, a failed job none), out_status by the caller's job index,
+// log: 3 int32 of scratch per MANDATORY pod; at the end the segment's residuals go back to res.
+hipError_t launch_place_min_domains(hipStream_t s, const PlaceGroup* groups, const PlaceMinOpt* opt,
+                                    const PlaceMinJob* jobs, const int32_t* job_start, int A, const PlaceSegs& segs,
+                                    int64_t* res, int64_t stride, uint64_t id_base, int32_t* out_pod, int32_t* out_status,
+                                    int32_t* out_group_pods, int32_t* log);
+
 // ---- first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_place.hip; the plan:
 // pe_first_fit_plan.h).  The member lists are launch_place_members'; the segments stay the working residuals of
 // their domains from round to round.

@@ -750,6 +750,40 @@ class Engine:
                                                    _p(st)), "pe_place_greedy_domains")
         return pod[:P], st[:J]
 
+    def place_min_member_domains(self, job_group_off, priority, group_count, group_req, group_need, min_member,
+                                 job_domain, level, level_size, parent=None):
+        """pe_place_min_member_domains: place_greedy_domains for gangs that are schedulable at min_member[j] pods
+        ([J]; PE_MIN_MEMBER_ALL = -1 or min_member None: the whole job).  The mandatory pods -- the job's first
+        min_member pod slots, plus the rest of an island group the cut falls in -- are placed all-or-nothing; after
+        that the optional pods of every group are placed as far as they fit, the rest of the group stays -1.
+        Residuals are updated in place.  Returns (pod_node [P], job_status [J], group_pods int32[G], job_pods
+        int64[J]): group_pods / job_pods count the pods that hold a node."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        mm = None if min_member is None else _c(min_member, np.int32)
+        if mm is not None and mm.shape != (J,):
+            raise ValueError("min_member must be [J]")
+        dom = None if job_domain is None else _c(job_domain, np.int32)
+        if dom is not None and dom.shape != (J,):
+            raise ValueError("job_domain must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        G = len(cnt)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        gp = np.zeros(max(G, 1), dtype=np.int32)
+        jp = np.zeros(max(J, 1), dtype=np.int64)
+        self._chk(self.lib.pe_place_min_member_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
+                                                       _p(nd), _p(mm), _p(dom), int(level), len(ls), _p(ls), _p(par),
+                                                       _p(pod), _p(st), _p(gp), _p(jp)), "pe_place_min_member_domains")
+        return pod[:P], st[:J], gp[:G], jp[:J]
+
     def gang_fit_domains(self, job_group_off, group_count, group_req, group_need, pair_job, pair_domain, level,
                          level_size, parent=None, tables=True, first=True) -> GangFit:
         """pe_gang_fit_domains: for every pair p, would place_greedy_domains place job pair_job[p] ALONE in the

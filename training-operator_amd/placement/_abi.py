@@ -98,6 +98,7 @@ SIGNATURES = {
     "pe_fit_mask_row_pitch": (ctypes.c_int, [P, ctypes.POINTER(i64)]),
     "pe_place_greedy": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P]),
     "pe_place_greedy_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, P, P]),
+    "pe_place_min_member_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_gang_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
     "pe_gang_preempt_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, P, P, i64, P, P, P, P, i32, i32, P, P,
