@@ -1,6 +1,7 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
-// pe_engine_capacity.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_preempt.cpp, pe_engine_ledger.cpp): device and pinned buffers, the helper threads, error mapping, input checks and
-// the context itself.  Not part of the ABI.
+// pe_engine_capacity.cpp, pe_domain_call.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_first_fit.cpp,
+// pe_engine_preempt.cpp, pe_engine_ledger.cpp): device and pinned buffers, the helper threads, error mapping, input
+// checks and the context itself.  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -394,59 +395,32 @@ struct pe_ctx {
   std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
   std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
   pe::SlicePlan sl_plan;                   // pe_gang_slice_tree: the call's rows and picks (its buffers are cp_* and lv_*)
-  // gang placement inside a domain (pe_place_greedy_domains, pe_engine_place.cpp).  Every call sizes and fills
-  // what it uses, so calls of any shape may alternate with every other entry point; nothing of the hierarchy
-  // or the batch outlives a call.  Grow and are reused.
-  HostBuf<uint8_t> pl_hin;      // one copy in: G PlaceGroup, J PlaceJob, then leaf_dom, act_of and job_start
-  DevBuf<uint8_t> pl_in;
-  DevBuf<int32_t> pl_out;       // one copy out: out_pod_node [P], then out_job_status [J]
-  HostBuf<int32_t> pl_hout;
-  DevBuf<int32_t> pl_log;       // the jobs' rollback logs, [P][3]
-  DevBuf<int32_t> pl_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
-  DevBuf<int64_t> pl_seg;       // the segments' residuals [4][stride]
-  DevBuf<uint32_t> pl_segw;     // their global ids and labels, [2][stride]
-  // exact what-if of a gang per domain (pe_gang_fit_domains, pe_engine_fit.cpp).  As pl_*: every call sizes and
-  // fills what it uses, nothing of the hierarchy, the batch or the pair list outlives a call.  Grow and are reused.
-  HostBuf<uint8_t> ft_hin;      // one copy in: G PlaceGroup, P FitPair, U FitUnit, then leaf_dom and act_of
-  DevBuf<uint8_t> ft_in;
-  DevBuf<uint8_t> ft_out;       // one copy out: out_first [J], then out_fits, out_fail_group, out_pods [P] (16-B aligned)
-  HostBuf<uint8_t> ft_hout;
-  DevBuf<int32_t> ft_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
-  DevBuf<int64_t> ft_seg;       // the segments' residuals [4][stride], read-only to the fit kernels
-  DevBuf<uint32_t> ft_segw;     // their global ids and labels, [2][stride]
-  HostBuf<int32_t> ft_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
-  hipEvent_t ft_ev = nullptr;   // ... and the event behind that copy: the host waits for it, not for the units behind it
-  HostBuf<uint8_t> ft_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
-  DevBuf<uint8_t> ft_large;
-  DevBuf<int64_t> ft_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
-  // which gangs must go for a gang to fit (pe_gang_preempt_domains, pe_engine_preempt.cpp).  As ft_*: every call
-  // sizes and fills what it uses, nothing of the hierarchy, the batch, the victims or the lists outlives a call.
-  HostBuf<uint8_t> pp_hin;      // one copy in: G PlaceGroup, P PrePair, U FitUnit, R PreRec, then the record CSR,
-  DevBuf<uint8_t> pp_in;        // the lists, leaf_dom and act_of
-  DevBuf<uint8_t> pp_out;       // one copy out: best [J] and the judgement counter (u64), then out_victims,
-  HostBuf<uint8_t> pp_hout;     // out_prefix and out_count [P] (16-B aligned)
-  DevBuf<int32_t> pp_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
-  DevBuf<int64_t> pp_seg;       // the segments' residuals [4][stride], read-only to the judging kernels
-  DevBuf<uint32_t> pp_segw;     // their global ids and labels, [2][stride]
-  DevBuf<int32_t> pp_place;     // node -> place in the segments' arrays [Ns], -1 = in no active domain
-  HostBuf<int32_t> pp_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
-  hipEvent_t pp_ev = nullptr;   // ... and the event behind that copy
-  HostBuf<uint8_t> pp_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
-  DevBuf<uint8_t> pp_large;
-  DevBuf<int64_t> pp_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
-  // first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_engine_first_fit.cpp).
-  // As pl_*: every call sizes and fills them anew.
-  HostBuf<uint8_t> ff_hin;      // one copy in: G PlaceGroup, J PlaceJob (by job index), P FirstFitEntry, then
-  DevBuf<uint8_t> ff_in;        // leaf_dom, act_of and q_start
-  DevBuf<int32_t> ff_out;       // one copy out: out_pod_node [P], then out_job_status [J] and out_job_pair [J]
-  HostBuf<int32_t> ff_hout;
-  DevBuf<int32_t> ff_log;       // the jobs' rollback logs, [P][3]
-  DevBuf<int32_t> ff_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
-  DevBuf<int64_t> ff_seg;       // the segments' residuals [4][stride]: the working residuals between rounds
-  DevBuf<uint32_t> ff_segw;     // their global ids and labels, [2][stride]
-  DevBuf<uint64_t> ff_state;    // the rounds' state: the jobs' words [J], the unsettled count, the queue cursors [A]
-  HostBuf<uint32_t> ff_hopen;   // the unsettled count read back
-  HostBuf<int32_t> ff_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
+  // the domain calls (pe_place_greedy_domains and pe_place_min_member_domains, pe_engine_place.cpp;
+  // pe_gang_fit_domains, pe_engine_fit.cpp; pe_place_first_fit_domains, pe_engine_first_fit.cpp;
+  // pe_gang_preempt_domains, pe_engine_preempt.cpp; their shared host path: pe_domain_call.h).  One set for all of
+  // them: calls on a context are serialised (guarded), and every call sizes and fills what it reads -- each span it
+  // reads back is written by its kernels or preset by its own memsets -- so calls of any shape may alternate with
+  // each other and with every other entry point; nothing of a hierarchy, a batch, a pair list or a victim list
+  // outlives a call.  Grow and are reused.
+  HostBuf<uint8_t> dm_hin;      // one copy in: the call's own block, G PlaceGroup first, the plan's words last (each
+  DevBuf<uint8_t> dm_in;        // unit's *_at offsets)
+  DevBuf<uint8_t> dm_out;       // one copy out: the call's answers, again in its own layout
+  HostBuf<uint8_t> dm_hout;
+  DevBuf<int32_t> dm_log;       // the placing calls' rollback logs, [pods][3]
+  DevBuf<int32_t> dm_dom;       // per active domain: node count [A], segment bounds [A + 1], fill cursor [A]
+  DevBuf<int64_t> dm_seg;       // the segments' residuals [4][stride]: read-only to the judging calls, the working
+                                // residuals of the placing ones
+  DevBuf<uint32_t> dm_segw;     // their global ids and labels, [2][stride]
+  HostBuf<int32_t> dm_hoff;     // the segment bounds read back (only when the shard has more than PL_LDS_NODES nodes)
+  hipEvent_t dm_ev = nullptr;   // ... and the event behind that copy: the host waits for it, not for the units behind it
+  HostBuf<uint8_t> dm_hlarge;   // the FitLarge records of the segments above PL_LDS_NODES nodes
+  DevBuf<uint8_t> dm_large;
+  DevBuf<int64_t> dm_scratch;   // their working copies: at most (1 + FIT_SCRATCH_MULT) x Ns nodes of 4 int64
+  DevBuf<int32_t> pp_place;     // pe_gang_preempt_domains: node -> place in the segments' arrays [Ns], -1 = in no
+                                // active domain
+  DevBuf<uint64_t> ff_state;    // pe_place_first_fit_domains: the rounds' state: the jobs' words [J], the unsettled
+                                // count, the queue cursors [A]
+  HostBuf<uint32_t> ff_hopen;   // ... and the unsettled count read back
   // giving back and re-taking placed gangs (pe_release_gangs, pe_assume_gangs, pe_engine_ledger.cpp): the plan with
   // its node -> scratch map (kept all -1 between calls, sized by the inventory) and the records of this shard's
   // touched nodes on their way in.  Grow and are reused; nothing of the gangs outlives a call.
@@ -526,17 +500,11 @@ struct pe_ctx {
     cp_hshapes.release(); cp_hout.release(); cp_shapes.release(); cp_part.release(); cp_out.release();
     lv_leaf.release(); lv_upper.release(); lv_hslots.release(); lv_hnodes.release();
     lv_hin.release(); lv_in.release(); lv_out.release(); lv_hout.release(); lv_split.release(); lv_hsplit.release();
-    pl_hin.release(); pl_in.release(); pl_out.release(); pl_hout.release(); pl_log.release(); pl_dom.release();
-    pl_seg.release(); pl_segw.release();
-    ft_hin.release(); ft_in.release(); ft_out.release(); ft_hout.release(); ft_dom.release(); ft_seg.release();
-    ft_segw.release(); ft_hoff.release(); ft_hlarge.release(); ft_large.release(); ft_scratch.release();
-    ff_hin.release(); ff_in.release(); ff_out.release(); ff_hout.release(); ff_log.release(); ff_dom.release();
-    ff_seg.release(); ff_segw.release(); ff_state.release(); ff_hopen.release(); ff_hoff.release();
-    pp_hin.release(); pp_in.release(); pp_out.release(); pp_hout.release(); pp_dom.release(); pp_seg.release();
-    pp_segw.release(); pp_place.release(); pp_hoff.release(); pp_hlarge.release(); pp_large.release(); pp_scratch.release();
+    dm_hin.release(); dm_in.release(); dm_out.release(); dm_hout.release(); dm_log.release(); dm_dom.release();
+    dm_seg.release(); dm_segw.release(); dm_hoff.release(); dm_hlarge.release(); dm_large.release(); dm_scratch.release();
+    pp_place.release(); ff_state.release(); ff_hopen.release();
     ld_hin.release(); ld_in.release();
-    if (ft_ev) (void)hipEventDestroy(ft_ev);
-    if (pp_ev) (void)hipEventDestroy(pp_ev);
+    if (dm_ev) (void)hipEventDestroy(dm_ev);
     for (hipEvent_t e : cp_ev)
       if (e) (void)hipEventDestroy(e);
     g_groups.release(); g_cand.release(); g_bound.release(); g_cnt.release(); g_out.release(); g_gath.release();
@@ -685,13 +653,13 @@ int64_t first_bad(int64_t n, Bad bad) {
 // (pe_engine.cpp)
 void check_req(const int64_t* req, int64_t n, const char* what);
 void check_offsets(const int32_t* off, int64_t n, int64_t limit, const char* what);
-// (pe_engine_place.cpp) What pe_place_greedy checks of a batch's groups (n_jobs > 0): the offsets, the counts
+// (pe_domain_call.cpp) What pe_place_greedy checks of a batch's groups (n_jobs > 0): the offsets, the counts
 // and the requests, with the first offending index; returns G.  And a refused hierarchy (pe_tree_plan.h
 // TreePlanError, `bad` its index) in pe_gang_capacity_tree's words.
 int64_t check_gang_groups(int64_t n_jobs, const int32_t* job_group_off, const int32_t* group_count,
                           const int64_t* group_req);
 [[noreturn]] void raise_tree(int tree_error, int64_t bad);
-// (pe_engine_place.cpp) What pe_place_greedy_domains checks of a batch (n_jobs > 0) and its outputs; returns G.
+// (pe_domain_call.cpp) What pe_place_greedy_domains checks of a batch (n_jobs > 0) and its outputs; returns G.
 int64_t check_place_batch(int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
                           const int32_t* group_count, const int64_t* group_req, const int32_t* out_pod_node,
                           const int32_t* out_job_status);

@@ -5,8 +5,9 @@
 // then ROUNDS work the queues off (launch_first_fit_round), several rounds queued per read-back of the count of
 // unsettled jobs, until that count is 0; one last kernel writes the segments back
 // to the live residuals.  The pod slots, statuses and pairs come back in one copy, and the host mirror and the
-// stats follow from that answer.  Own buffers (pe_ctx.h ff_*): nothing of the call is kept.
-#include "pe_ctx.h"
+// stats follow from that answer.  The host path and the buffers are the domain calls' (pe_domain_call.h, pe_ctx.h
+// dm_*, ff_state and ff_hopen): nothing of the call is kept.
+#include "pe_domain_call.h"
 #include "pe_first_fit_plan.h"
 
 // Rounds queued per read-back of the unsettled count: FF_ROUNDS_FIRST before the first read-back, twice as many
@@ -23,22 +24,6 @@
 static_assert(FF_ROUNDS_FIRST >= 1 && FF_ROUNDS_MAX >= FF_ROUNDS_FIRST, "FF_ROUNDS_FIRST, FF_ROUNDS_MAX");
 static_assert(sizeof(pe::FirstFitCand) == sizeof(pe::FirstFitEntry), "the plan's queue entry is the device's");
 
-namespace {
-
-[[noreturn]] void raise_plan(pe::FitPlanError e, pe::TreePlanError te, int64_t bad) {
-  switch (e) {
-    case pe::FIT_BAD_LEVEL: raise(PE_EINVAL, "level outside [0, n_levels)");
-    case pe::FIT_BAD_COUNT: raise(PE_EINVAL, "n_pairs outside [0, 2^31 - 1)");
-    case pe::FIT_NO_PAIRS: raise(PE_EINVAL, "pair_job or pair_domain is NULL");
-    case pe::FIT_BAD_JOB: raise(PE_EINVAL, "pair_job: value outside [0, n_jobs) at index " + std::to_string(bad));
-    case pe::FIT_BAD_DOMAIN:
-      raise(PE_EINVAL, "pair_domain: value outside [0, level_size[level]) at index " + std::to_string(bad));
-    default: raise_tree(te, bad);
-  }
-}
-
-}  // namespace
-
 extern "C" {
 
 int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
@@ -47,10 +32,7 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
                                int32_t n_levels, const int32_t* level_size, const int32_t* parent,
                                int32_t* out_pod_node, int32_t* out_job_status, int32_t* out_job_pair) {
   return guarded(ctx, [&]() -> int {
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    if (ctx->world > 1)
-      raise(PE_EINVAL, "pe_place_first_fit_domains on a sharded context: a domain may span shards");
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    domain_entry_checks(ctx, "pe_place_first_fit_domains", n_jobs);
     const int64_t G =
         n_jobs > 0 ? check_place_batch(n_jobs, job_group_off, priority, group_count, group_req, out_pod_node, out_job_status)
                    : 0;
@@ -59,7 +41,7 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
     int64_t bad = -1;
     const pe::FitPlanError err = pe::first_fit_plan_build(plan, n_jobs, job_group_off, priority, group_count, n_pairs,
                                                           pair_job, pair_domain, level, n_levels, level_size, parent, &te, &bad);
-    if (err != pe::FIT_OK) raise_plan(err, te, bad);
+    if (err != pe::FIT_OK) raise_fit_plan(err, te, bad);
     if (n_jobs == 0) return PE_OK;
 
     const int64_t J = n_jobs, NP = n_pairs, A = plan.n_active(), P = plan.pods();
@@ -79,54 +61,33 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
     const size_t queue_at = jobs_at + (size_t)J * sizeof(pe::PlaceJob);
     const size_t words_at = queue_at + (size_t)NP * sizeof(pe::FirstFitEntry);
     const size_t in_bytes = words_at + (size_t)(L0 + ND + A + 1) * sizeof(int32_t);
-    hipchk(ctx->ff_hin.ensure(in_bytes), "alloc pinned first-fit inputs");
-    hipchk(ctx->ff_in.ensure(in_bytes), "alloc first-fit inputs");
-    pe::PlaceGroup* const h_groups = (pe::PlaceGroup*)ctx->ff_hin.p;
-    for (int64_t g = 0; g < G; ++g) {
-      pe::PlaceGroup& r = h_groups[g];
-      std::memset(&r, 0, sizeof(r));
-      for (int d = 0; d < pe::D; ++d) r.q[d] = group_req[g * pe::D + d];
-      r.need = group_need ? group_need[g] : 0u;
-      r.count = group_count[g];
-      r.pod0 = plan.pod_off[(size_t)g];
-    }
-    pe::PlaceJob* const h_jobs = (pe::PlaceJob*)(ctx->ff_hin.p + jobs_at);
+    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned first-fit inputs");
+    hipchk(ctx->dm_in.ensure(in_bytes), "alloc first-fit inputs");
+    fill_place_groups((pe::PlaceGroup*)ctx->dm_hin.p, G, group_req, group_need, group_count, plan.pod_off.data());
+    pe::PlaceJob* const h_jobs = (pe::PlaceJob*)(ctx->dm_hin.p + jobs_at);
     for (int64_t j = 0; j < J; ++j) h_jobs[j] = pe::PlaceJob{(int32_t)j, job_group_off[j], job_group_off[j + 1], 0};
-    std::memcpy(ctx->ff_hin.p + queue_at, plan.queue.data(), (size_t)NP * sizeof(pe::FirstFitEntry));
-    int32_t* const h_words = (int32_t*)(ctx->ff_hin.p + words_at);
-    std::memcpy(h_words, plan.leaf_dom.data(), (size_t)L0 * sizeof(int32_t));
-    std::memcpy(h_words + L0, plan.act_of.data(), (size_t)ND * sizeof(int32_t));
-    std::memcpy(h_words + L0 + ND, plan.q_start.data(), (size_t)(A + 1) * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->ff_in.p, ctx->ff_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
+    std::memcpy(ctx->dm_hin.p + queue_at, plan.queue.data(), (size_t)NP * sizeof(pe::FirstFitEntry));
+    int32_t* const h_q_start = pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), plan.leaf_dom, plan.act_of);
+    std::memcpy(h_q_start, plan.q_start.data(), (size_t)(A + 1) * sizeof(int32_t));
+    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
            "H2D first-fit inputs");
-    const pe::PlaceGroup* const d_groups = (const pe::PlaceGroup*)ctx->ff_in.p;
-    const pe::PlaceJob* const d_jobs = (const pe::PlaceJob*)(ctx->ff_in.p + jobs_at);
-    const pe::FirstFitEntry* const d_queue = (const pe::FirstFitEntry*)(ctx->ff_in.p + queue_at);
-    const int32_t* const d_words = (const int32_t*)(ctx->ff_in.p + words_at);
+    const pe::PlaceGroup* const d_groups = (const pe::PlaceGroup*)ctx->dm_in.p;
+    const pe::PlaceJob* const d_jobs = (const pe::PlaceJob*)(ctx->dm_in.p + jobs_at);
+    const pe::FirstFitEntry* const d_queue = (const pe::FirstFitEntry*)(ctx->dm_in.p + queue_at);
+    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
     const int32_t* const d_q_start = d_words + L0 + ND;
     // ---- the call's device buffers; the answers: pods [P], pairs [J], statuses [J]
-    const int64_t st = std::max<int64_t>(ctx->stride, 1);
-    hipchk(ctx->ff_out.ensure((size_t)(P + 2 * J)), "alloc first-fit outputs");
-    hipchk(ctx->ff_hout.ensure((size_t)(P + 2 * J)), "alloc pinned first-fit outputs");
-    hipchk(ctx->ff_log.ensure((size_t)(3 * P)), "alloc first-fit logs");
-    hipchk(ctx->ff_dom.ensure((size_t)(3 * A + 1)), "alloc domain lists");
-    hipchk(ctx->ff_seg.ensure((size_t)(pe::D * st)), "alloc domain segments");
-    hipchk(ctx->ff_segw.ensure((size_t)(2 * st)), "alloc domain segments");
+    const size_t out_bytes = (size_t)(P + 2 * J) * sizeof(int32_t);
+    hipchk(ctx->dm_out.ensure(out_bytes), "alloc first-fit outputs");
+    hipchk(ctx->dm_hout.ensure(out_bytes), "alloc pinned first-fit outputs");
+    hipchk(ctx->dm_log.ensure((size_t)(3 * P)), "alloc first-fit logs");
     hipchk(ctx->ff_state.ensure((size_t)(J + 1 + (A + 1) / 2)), "alloc first-fit state");
     hipchk(ctx->ff_hopen.ensure(1), "alloc pinned unsettled count");
-    pe::PlaceSegs segs{};
-    segs.cnt = ctx->ff_dom.p;
-    segs.seg_off = ctx->ff_dom.p + A;
-    segs.cursor = ctx->ff_dom.p + 2 * A + 1;
-    segs.gid = ctx->ff_segw.p;
-    segs.lab = ctx->ff_segw.p + st;
-    segs.res = ctx->ff_seg.p;
-    segs.seg_stride = st;
+    const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::FirstFitState state{ctx->ff_state.p, (int32_t*)(ctx->ff_state.p + J + 1), (uint32_t*)(ctx->ff_state.p + J)};
-    int32_t* const d_pods = ctx->ff_out.p;
-    int32_t* const d_pair = ctx->ff_out.p + P;
-    int32_t* const d_status = ctx->ff_out.p + P + J;
-    hipchk(hipMemsetAsync(segs.cnt, 0, (size_t)A * sizeof(int32_t), ctx->stream), "zero domain counts");
+    int32_t* const d_pods = (int32_t*)ctx->dm_out.p;
+    int32_t* const d_pair = d_pods + P;
+    int32_t* const d_status = d_pods + P + J;
     hipchk(hipMemsetAsync(state.word, 0, (size_t)(J + 1) * sizeof(uint64_t), ctx->stream), "zero first-fit state");
     hipchk(hipMemsetD32Async((hipDeviceptr_t)state.open, (int)with_cand, 1, ctx->stream), "set unsettled count");
     hipchk(hipMemcpyAsync(state.cursor, d_q_start, (size_t)A * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream),
@@ -136,21 +97,15 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
            "preset statuses");
     CapEvents ev(ctx);
     ev.begin();
-    hipchk(pe::launch_place_members(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
-                                    (uint64_t)ctx->begin, d_words, (int)L0, d_words + L0, (int)A, segs),
-           "launch place_members");
+    launch_domain_members(ctx, d_words, L0, A, segs);
     // which of the round kernel's two instances have a segment to work on: every segment is small when the shard
     // is; otherwise the bounds come back once, and an instance without segments is never launched
     int kinds = pe::FF_SMALL;
-    if (ctx->Ns > pe::PL_LDS_NODES) {
-      hipchk(ctx->ff_hoff.ensure((size_t)(A + 1)), "alloc pinned segment bounds");
-      hipchk(hipMemcpyAsync(ctx->ff_hoff.p, segs.seg_off, (size_t)(A + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
-                            ctx->stream),
-             "D2H segment bounds");
+    if (queue_segment_bounds(ctx, segs, A)) {
       hipchk(hipStreamSynchronize(ctx->stream), "sync segment bounds");
       kinds = 0;
       for (int64_t a = 0; a < A; ++a)
-        kinds |= ctx->ff_hoff.p[a + 1] - ctx->ff_hoff.p[a] > pe::PL_LDS_NODES ? pe::FF_LARGE : pe::FF_SMALL;
+        kinds |= ctx->dm_hoff.p[a + 1] - ctx->dm_hoff.p[a] > pe::PL_LDS_NODES ? pe::FF_LARGE : pe::FF_SMALL;
     }
     // ---- the rounds: at most n_pairs + 1 (every round attempts the lowest-ranked unsettled job at least)
     const int64_t max_rounds = NP + 1;
@@ -163,7 +118,7 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
       per_read = std::min<int64_t>(2 * per_read, FF_ROUNDS_MAX);
       for (; rounds < upto; ++rounds)
         hipchk(pe::launch_first_fit_round(ctx->stream, d_groups, d_jobs, d_q_start, d_queue, (int)A, segs, kinds,
-                                          (uint32_t)(rounds + 1), state, d_pods, d_status, d_pair, ctx->ff_log.p),
+                                          (uint32_t)(rounds + 1), state, d_pods, d_status, d_pair, ctx->dm_log.p),
                "launch first_fit_round");
       hipchk(hipMemcpyAsync(ctx->ff_hopen.p, state.open, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
              "D2H unsettled count");
@@ -173,39 +128,16 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
     hipchk(pe::launch_first_fit_finish(ctx->stream, segs, (int)A, ctx->Ns, ctx->res.p, ctx->stride, (uint64_t)ctx->begin),
            "launch first_fit_finish");
     ev.end();
-    hipchk(hipMemcpyAsync(ctx->ff_hout.p, ctx->ff_out.p, (size_t)(P + 2 * J) * sizeof(int32_t), hipMemcpyDeviceToHost,
-                          ctx->stream),
+    hipchk(hipMemcpyAsync(ctx->dm_hout.p, ctx->dm_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream),
            "D2H first-fit answers");
     hipchk(hipStreamSynchronize(ctx->stream), "sync place_first_fit_domains");
-    const int32_t* const pods = ctx->ff_hout.p;
-    const int32_t* const pair = ctx->ff_hout.p + P;
-    const int32_t* const status = ctx->ff_hout.p + P + J;
+    const int32_t* const pods = (const int32_t*)ctx->dm_hout.p;
+    const int32_t* const pair = pods + P;
+    const int32_t* const status = pods + P + J;
     if (P > 0) std::memcpy(out_pod_node, pods, (size_t)P * sizeof(int32_t));
     std::memcpy(out_job_status, status, (size_t)J * sizeof(int32_t));
     if (out_job_pair) std::memcpy(out_job_pair, pair, (size_t)J * sizeof(int32_t));
-    // ---- the mirror follows the answer: the request off every placed pod's node, a run of one node at a time
-    int64_t placed_pods = 0, placed = 0;
-    for (int64_t j = 0; j < J; ++j) {
-      if (status[j] != PE_JOB_PLACED) continue;
-      ++placed;
-      for (int64_t g = job_group_off[j]; g < job_group_off[j + 1]; ++g) {
-        const int64_t p0 = plan.pod_off[(size_t)g], p1 = plan.pod_off[(size_t)g + 1];
-        const int64_t* q = group_req + g * pe::D;
-        placed_pods += p1 - p0;
-        for (int64_t p = p0; p < p1;) {
-          const int32_t node = pods[p];
-          int64_t e = p + 1;
-          while (e < p1 && pods[e] == node) ++e;
-          if (node < 0 || node >= ctx->n_total) raise(PE_EHIP, "first_fit_round_kernel: a placed pod without a node");
-          pe::NodeState& ns = ctx->m_nodes[(size_t)node];
-          for (int d = 0; d < pe::D; ++d) ns.res[d] -= (e - p) * q[d];
-          p = e;
-        }
-      }
-    }
-    ctx->stats.pods_placed += placed_pods;
-    ctx->stats.jobs_placed += placed;
-    ctx->stats.jobs_failed += J - placed;
+    mirror_follow(ctx, "first_fit_round_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods, status);
     ev.report_as("A=" + std::to_string(A) + " rounds=" + std::to_string(rounds));
     return PE_OK;
   });

@@ -5,29 +5,17 @@
 // nodes into a compact segment, one small kernel maps every node to its place there, and the kernels of
 // pe_preempt.hip walk every pair through the two phases, one workgroup per unit of at most PRE_UNIT_PAIRS pairs;
 // the answers the caller asked for come back in one copy.  Read-only: the device residuals, the host mirror, the
-// reset snapshot, the staged fit-mask state and the stats are not touched.  Own buffers (pe_ctx.h pp_*): nothing
-// of the call is kept between calls.
-#include "pe_ctx.h"
+// reset snapshot, the staged fit-mask state and the stats are not touched.  The host path and the buffers are the
+// domain calls' (pe_domain_call.h, pe_ctx.h dm_* and pp_place): nothing of the call is kept between calls.
+#include "pe_domain_call.h"
 #include "pe_preempt_plan.h"
 
 namespace {
 
-[[noreturn]] void raise_fit(pe::FitPlanError e, pe::TreePlanError te, int64_t bad) {
-  switch (e) {
-    case pe::FIT_BAD_LEVEL: raise(PE_EINVAL, "level outside [0, n_levels)");
-    case pe::FIT_BAD_COUNT: raise(PE_EINVAL, "n_pairs outside [0, 2^31 - 1)");
-    case pe::FIT_NO_PAIRS: raise(PE_EINVAL, "pair_job or pair_domain is NULL");
-    case pe::FIT_BAD_JOB: raise(PE_EINVAL, "pair_job: value outside [0, n_jobs) at index " + std::to_string(bad));
-    case pe::FIT_BAD_DOMAIN:
-      raise(PE_EINVAL, "pair_domain: value outside [0, level_size[level]) at index " + std::to_string(bad));
-    default: raise_tree(te, bad);
-  }
-}
-
 [[noreturn]] void raise_plan(pe::PreemptPlanError e, pe::FitPlanError fe, pe::TreePlanError te, int64_t bad) {
   const std::string at = " at index " + std::to_string(bad);
   switch (e) {
-    case pe::PRE_BAD_FIT: raise_fit(fe, te, bad);
+    case pe::PRE_BAD_FIT: raise_fit_plan(fe, te, bad);
     case pe::PRE_BAD_VICTIMS: raise(PE_EINVAL, "n_victims outside [0, 2^31 - 1]");
     case pe::PRE_NO_VIC_OFF: raise(PE_EINVAL, "vic_group_off is NULL");
     case pe::PRE_BAD_VIC_OFF: raise(PE_EINVAL, "vic_group_off: not rising from 0" + at);
@@ -46,8 +34,6 @@ namespace {
   }
 }
 
-size_t r16(size_t x) { return (x + 15) & ~size_t(15); }
-
 }  // namespace
 
 extern "C" {
@@ -60,9 +46,7 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                             int32_t level, int32_t n_levels, const int32_t* level_size, const int32_t* parent,
                             int32_t* out_prefix, uint64_t* out_victims, int32_t* out_count, int32_t* out_best) {
   return guarded(ctx, [&]() -> int {
-    if (!ctx->loaded) raise(PE_ESTATE, "no inventory loaded");
-    if (ctx->world > 1) raise(PE_EINVAL, "pe_gang_preempt_domains on a sharded context: a domain may span shards");
-    if (n_jobs < 0) raise(PE_EINVAL, "n_jobs < 0");
+    domain_entry_checks(ctx, "pe_gang_preempt_domains", n_jobs);
     const int64_t G = n_jobs > 0 ? check_gang_groups(n_jobs, job_group_off, group_count, group_req) : 0;
     pe::PreemptPlan plan;
     pe::FitPlanError fe = pe::FIT_OK;
@@ -100,111 +84,63 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
     const size_t list_at = rstart_at + (size_t)(V + 1) * sizeof(int32_t);
     const size_t words_at = list_at + (size_t)NL * sizeof(int32_t);
     const size_t in_bytes = words_at + (size_t)(L0 + ND) * sizeof(int32_t);
-    hipchk(ctx->pp_hin.ensure(in_bytes), "alloc pinned gang-preempt inputs");
-    hipchk(ctx->pp_in.ensure(in_bytes), "alloc gang-preempt inputs");
-    pe::PlaceGroup* const h_groups = (pe::PlaceGroup*)ctx->pp_hin.p;
-    for (int64_t g = 0; g < G; ++g) {
-      pe::PlaceGroup& r = h_groups[g];
-      std::memset(&r, 0, sizeof(r));
-      for (int d = 0; d < pe::D; ++d) r.q[d] = group_req[g * pe::D + d];
-      r.need = group_need ? group_need[g] : 0u;
-      r.count = group_count[g];
-    }
-    pe::PrePair* const h_pairs = (pe::PrePair*)(ctx->pp_hin.p + pairs_at);
+    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned gang-preempt inputs");
+    hipchk(ctx->dm_in.ensure(in_bytes), "alloc gang-preempt inputs");
+    fill_place_groups((pe::PlaceGroup*)ctx->dm_hin.p, G, group_req, group_need, group_count, nullptr);
+    pe::PrePair* const h_pairs = (pe::PrePair*)(ctx->dm_hin.p + pairs_at);
     for (int64_t i = 0; i < P; ++i) {
       const int32_t p = fit.pairs[(size_t)i], j = pair_job[p];
       h_pairs[i] = pe::PrePair{p, j, job_group_off[j], job_group_off[j + 1], plan.list_start[(size_t)i],
                                plan.list_start[(size_t)i + 1], {0, 0}};
     }
-    std::memcpy(ctx->pp_hin.p + units_at, fit.units.data(), (size_t)U * sizeof(pe::FitUnit));
-    std::memcpy(ctx->pp_hin.p + recs_at, plan.recs.data(), (size_t)R * sizeof(pe::PreRec));
-    std::memcpy(ctx->pp_hin.p + rstart_at, plan.rec_start.data(), (size_t)(V + 1) * sizeof(int32_t));
-    std::memcpy(ctx->pp_hin.p + list_at, plan.list.data(), (size_t)NL * sizeof(int32_t));
-    int32_t* const h_words = (int32_t*)(ctx->pp_hin.p + words_at);
-    std::memcpy(h_words, fit.leaf_dom.data(), (size_t)L0 * sizeof(int32_t));
-    std::memcpy(h_words + L0, fit.act_of.data(), (size_t)ND * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->pp_in.p, ctx->pp_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
+    std::memcpy(ctx->dm_hin.p + units_at, fit.units.data(), (size_t)U * sizeof(pe::FitUnit));
+    std::memcpy(ctx->dm_hin.p + recs_at, plan.recs.data(), (size_t)R * sizeof(pe::PreRec));
+    std::memcpy(ctx->dm_hin.p + rstart_at, plan.rec_start.data(), (size_t)(V + 1) * sizeof(int32_t));
+    std::memcpy(ctx->dm_hin.p + list_at, plan.list.data(), (size_t)NL * sizeof(int32_t));
+    pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), fit.leaf_dom, fit.act_of);
+    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
            "H2D gang-preempt inputs");
-    const int32_t* const d_words = (const int32_t*)(ctx->pp_in.p + words_at);
+    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
     // ---- the call's device buffers; the answers: best [J] and the judgement counter (64-bit cells), then victims,
     // prefix and count [P], 16-B aligned
-    const int64_t st = std::max<int64_t>(ctx->stride, 1);
     const size_t judged_at = (size_t)J * sizeof(uint64_t);
     const size_t vict_at = r16(judged_at + sizeof(uint64_t));
     const size_t prefix_at = vict_at + r16((size_t)P * sizeof(uint64_t));
     const size_t count_at = prefix_at + r16((size_t)P * sizeof(int32_t));
     const size_t out_bytes = count_at + (size_t)P * sizeof(int32_t);
-    hipchk(ctx->pp_out.ensure(out_bytes), "alloc gang-preempt outputs");
-    hipchk(ctx->pp_dom.ensure((size_t)(3 * A + 1)), "alloc domain lists");
-    hipchk(ctx->pp_seg.ensure((size_t)(pe::D * st)), "alloc domain segments");
-    hipchk(ctx->pp_segw.ensure((size_t)(2 * st)), "alloc domain segments");
+    hipchk(ctx->dm_out.ensure(out_bytes), "alloc gang-preempt outputs");
     hipchk(ctx->pp_place.ensure((size_t)std::max<int64_t>(ctx->Ns, 1)), "alloc node places");
-    pe::PlaceSegs segs{};
-    segs.cnt = ctx->pp_dom.p;
-    segs.seg_off = ctx->pp_dom.p + A;
-    segs.cursor = ctx->pp_dom.p + 2 * A + 1;
-    segs.gid = ctx->pp_segw.p;
-    segs.lab = ctx->pp_segw.p + st;
-    segs.res = ctx->pp_seg.p;
-    segs.seg_stride = st;
+    const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::PreIn in{};
-    in.groups = (const pe::PlaceGroup*)ctx->pp_in.p;
-    in.pairs = (const pe::PrePair*)(ctx->pp_in.p + pairs_at);
-    in.units = (const pe::FitUnit*)(ctx->pp_in.p + units_at);
-    in.recs = (const pe::PreRec*)(ctx->pp_in.p + recs_at);
-    in.rec_start = (const int32_t*)(ctx->pp_in.p + rstart_at);
-    in.list = (const int32_t*)(ctx->pp_in.p + list_at);
+    in.groups = (const pe::PlaceGroup*)ctx->dm_in.p;
+    in.pairs = (const pe::PrePair*)(ctx->dm_in.p + pairs_at);
+    in.units = (const pe::FitUnit*)(ctx->dm_in.p + units_at);
+    in.recs = (const pe::PreRec*)(ctx->dm_in.p + recs_at);
+    in.rec_start = (const int32_t*)(ctx->dm_in.p + rstart_at);
+    in.list = (const int32_t*)(ctx->dm_in.p + list_at);
     in.node_place = ctx->pp_place.p;
     in.Ns = ctx->Ns;
     in.id_base = (uint64_t)ctx->begin;
-    pe::PreOut out{(unsigned long long*)ctx->pp_out.p, (unsigned long long*)(ctx->pp_out.p + judged_at),
-                   (uint64_t*)(ctx->pp_out.p + vict_at), (int32_t*)(ctx->pp_out.p + prefix_at),
-                   (int32_t*)(ctx->pp_out.p + count_at)};
-    hipchk(hipMemsetAsync(segs.cnt, 0, (size_t)A * sizeof(int32_t), ctx->stream), "zero domain counts");
+    pe::PreOut out{(unsigned long long*)ctx->dm_out.p, (unsigned long long*)(ctx->dm_out.p + judged_at),
+                   (uint64_t*)(ctx->dm_out.p + vict_at), (int32_t*)(ctx->dm_out.p + prefix_at),
+                   (int32_t*)(ctx->dm_out.p + count_at)};
     hipchk(hipMemsetAsync(out.best, 0xFF, judged_at, ctx->stream), "clear best pairs");
     hipchk(hipMemsetAsync(out.judged, 0, sizeof(uint64_t), ctx->stream), "zero the judgement counter");
     if (ctx->Ns > 0)
       hipchk(hipMemsetAsync(ctx->pp_place.p, 0xFF, (size_t)ctx->Ns * sizeof(int32_t), ctx->stream), "clear node places");
     CapEvents ev(ctx);
     ev.begin();
-    hipchk(pe::launch_place_members(ctx->stream, ctx->res.p, ctx->stride, ctx->labels.p, ctx->island.p, ctx->Ns,
-                                    (uint64_t)ctx->begin, d_words, (int)L0, d_words + L0, (int)A, segs),
-           "launch place_members");
+    launch_domain_members(ctx, d_words, L0, A, segs);
     hipchk(pe::launch_preempt_place_map(ctx->stream, segs, (int)A, ctx->Ns, (uint64_t)ctx->begin, ctx->pp_place.p),
            "launch preempt_place_map");
     // a segment above PL_LDS_NODES nodes needs the shard to have that many: only then the bounds come back, while
     // the units of the smaller segments already run
-    const bool may_be_large = ctx->Ns > pe::PL_LDS_NODES;
-    if (may_be_large) {
-      hipchk(ctx->pp_hoff.ensure((size_t)(A + 1)), "alloc pinned segment bounds");
-      hipchk(hipMemcpyAsync(ctx->pp_hoff.p, segs.seg_off, (size_t)(A + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
-                            ctx->stream),
-             "D2H segment bounds");
-      if (!ctx->pp_ev) hipchk(hipEventCreateWithFlags(&ctx->pp_ev, hipEventDisableTiming), "event create");
-      hipchk(hipEventRecord(ctx->pp_ev, ctx->stream), "event record");
-    }
+    large_segments_begin(ctx, segs, A);
     hipchk(pe::launch_preempt_units(ctx->stream, in, U, segs, out), "launch preempt_domains (LDS)");
-    if (may_be_large) {
-      hipchk(hipEventSynchronize(ctx->pp_ev), "wait for the segment bounds");
-      std::vector<pe::FitLarge> large;
-      const int64_t nodes = pe::fit_scratch_layout(fit, ctx->pp_hoff.p, ctx->Ns, pe::PL_LDS_NODES, large);
-      if (!large.empty()) {
-        const size_t bytes = large.size() * sizeof(pe::FitLarge);
-        hipchk(ctx->pp_hlarge.ensure(bytes), "alloc pinned large-segment records");
-        hipchk(ctx->pp_large.ensure(bytes), "alloc large-segment records");
-        if (ctx->pp_scratch.ensure((size_t)(pe::D * nodes)) != hipSuccess) {
-          (void)hipGetLastError();
-          (void)hipStreamSynchronize(ctx->stream);   // the units already queued touch the call's own buffers only
-          raise(PE_ENOMEM, "working copies of the large segments: device allocation failed");
-        }
-        std::memcpy(ctx->pp_hlarge.p, large.data(), bytes);
-        hipchk(hipMemcpyAsync(ctx->pp_large.p, ctx->pp_hlarge.p, bytes, hipMemcpyHostToDevice, ctx->stream),
-               "H2D large-segment records");
-        hipchk(pe::launch_preempt_large(ctx->stream, in, (const pe::FitLarge*)ctx->pp_large.p, (int64_t)large.size(),
-                                        ctx->pp_scratch.p, segs, out),
-               "launch preempt_domains (global)");
-      }
-    }
+    const LargeSegs large = large_segments(ctx, fit);
+    if (large.n > 0)
+      hipchk(pe::launch_preempt_large(ctx->stream, in, large.recs, large.n, large.scratch, segs, out),
+             "launch preempt_domains (global)");
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for (the judgement counter
     // lies behind best and crosses with it, or alone for the diagnostics)
@@ -214,12 +150,12 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                       : out_victims ? vict_at + (size_t)P * sizeof(uint64_t)
                                     : judged_at + sizeof(uint64_t);
     if (out_best || out_victims || out_prefix || out_count || ev.on) {
-      hipchk(ctx->pp_hout.ensure(hi), "alloc pinned gang-preempt outputs");
-      hipchk(hipMemcpyAsync(ctx->pp_hout.p + lo, ctx->pp_out.p + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream),
+      hipchk(ctx->dm_hout.ensure(hi), "alloc pinned gang-preempt outputs");
+      hipchk(hipMemcpyAsync(ctx->dm_hout.p + lo, ctx->dm_out.p + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream),
              "D2H gang-preempt answers");
     }
     hipchk(hipStreamSynchronize(ctx->stream), "sync gang_preempt_domains");
-    const uint8_t* const h = ctx->pp_hout.p;
+    const uint8_t* const h = ctx->dm_hout.p;
     if (out_best) {   // the low half of the minimum is the pair; ~0 reads as -1: no pair has an answer
       const uint64_t* const best = (const uint64_t*)h;
       for (int64_t j = 0; j < J; ++j) out_best[j] = (int32_t)(uint32_t)best[j];

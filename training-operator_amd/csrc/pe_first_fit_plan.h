@@ -59,32 +59,20 @@ inline FitPlanError first_fit_plan_build(FirstFitPlan& plan, int64_t n_jobs, con
   std::stable_sort(order.begin(), order.end(), [priority](int32_t a, int32_t b) { return priority[a] > priority[b]; });
   p.rank.resize((size_t)n_jobs);
   for (int64_t i = 0; i < n_jobs; ++i) p.rank[(size_t)order[(size_t)i]] = (int32_t)i;
-  // every job's candidates in ascending p (a counting sort)
-  p.cand_start.assign((size_t)n_jobs + 1, 0);
-  for (int64_t q = 0; q < n_pairs; ++q) ++p.cand_start[(size_t)pair_job[q] + 1];
-  for (int64_t j = 0; j < n_jobs; ++j) p.cand_start[(size_t)j + 1] += p.cand_start[(size_t)j];
-  {
-    std::vector<int32_t> fill(p.cand_start.begin(), p.cand_start.end() - 1);
-    p.cand.resize((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; ++q) p.cand[(size_t)fill[(size_t)pair_job[q]]++] = (int32_t)q;
-  }
-  // the queues: the entries dealt to their domains job by job in rank order, candidate by candidate, so every
-  // queue comes out sorted by (rank, k); fit's pair_start already holds the bounds
+  // every job's candidates in ascending p; then the queues: the entries dealt to their domains job by job in rank
+  // order, candidate by candidate, so every queue comes out sorted by (rank, k); fit's pair_start holds the bounds
+  csr_deal((size_t)n_jobs, n_pairs, [&](int64_t q) { return pair_job[q]; }, nullptr, p.cand_start, p.cand);
   p.q_start = std::move(fit.pair_start);
-  {
-    std::vector<int32_t> fill(p.q_start.begin(), p.q_start.end() - 1);
-    p.queue.resize((size_t)n_pairs);
-    for (int32_t j : order) {
-      const int32_t c0 = p.cand_start[(size_t)j], c1 = p.cand_start[(size_t)j + 1];
-      for (int32_t c = c0; c < c1; ++c) {
-        const int32_t q = p.cand[(size_t)c];
-        p.queue[(size_t)fill[(size_t)p.act_of[(size_t)pair_domain[q]]]++] = FirstFitCand{j, c - c0, q, c + 1 == c1};
-      }
+  std::vector<int32_t> fill(p.q_start.begin(), p.q_start.end() - 1);
+  p.queue.resize((size_t)n_pairs);
+  for (int32_t j : order) {
+    const int32_t c0 = p.cand_start[(size_t)j], c1 = p.cand_start[(size_t)j + 1];
+    for (int32_t c = c0; c < c1; ++c) {
+      const int32_t q = p.cand[(size_t)c];
+      p.queue[(size_t)fill[(size_t)p.act_of[(size_t)pair_domain[q]]]++] = FirstFitCand{j, c - c0, q, c + 1 == c1};
     }
   }
-  const int64_t G = n_jobs > 0 ? job_group_off[n_jobs] : 0;
-  p.pod_off.assign((size_t)G + 1, 0);
-  for (int64_t g = 0; g < G; ++g) p.pod_off[(size_t)g + 1] = p.pod_off[(size_t)g] + group_count[g];
+  p.pod_off = pod_offsets(n_jobs > 0 ? job_group_off[n_jobs] : 0, group_count);
   plan = std::move(p);
   return FIT_OK;
 }

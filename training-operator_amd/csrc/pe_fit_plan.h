@@ -3,9 +3,7 @@
 // tests/cpp/test_fit_plan.cc builds it under the sanitizers.
 //
 // The hierarchy is pe_gang_capacity_tree's (pe_tree_plan.h validates it).  For the call's `level` the plan holds
-//   leaf_dom[size[0]]    the level-`level` domain of leaf domain k, walked up the parent map; -1 = none
-//   act_of[size[level]]  the ACTIVE index of a level-`level` domain (active = named by some pair), -1 = inactive
-//   active[A]            the active domains' ids, ascending
+//   leaf_dom, act_of, active[A]   pe_domain_map.h's maps; a domain is active when some pair names it
 //   pair_start[A + 1], pairs[P]   CSR from active domain to its pairs, ascending p within a domain
 //   unit_start[A + 1], units[U]   the WORK UNITS: domain a's CSR range cut into runs of at most FIT_UNIT_PAIRS
 //                        places, units[unit_start[a] .. unit_start[a + 1]) in ascending order of the range
@@ -16,9 +14,8 @@
 #define PE_FIT_PLAN_H_
 
 #include <algorithm>
-#include <numeric>
 
-#include "pe_tree_plan.h"
+#include "pe_domain_map.h"
 
 namespace pe {
 
@@ -84,28 +81,9 @@ inline FitPlanError fit_plan_build(FitPlan& plan, int64_t n_jobs, int64_t n_pair
   f.level = level;
   f.n_leaf = tree.size[0];
   f.n_dom = n_dom;
-  // leaf -> level: one step up the parent map per level
-  f.leaf_dom.resize((size_t)f.n_leaf);
-  std::iota(f.leaf_dom.begin(), f.leaf_dom.end(), 0);
-  for (int l = 0; l < level; ++l)
-    for (int32_t& d : f.leaf_dom)
-      if (d >= 0) d = parent[tree.off[l] + d];
-  // active domains, ascending
-  f.act_of.assign((size_t)n_dom, -1);
-  for (int64_t p = 0; p < n_pairs; ++p) f.act_of[(size_t)pair_domain[p]] = 0;
-  for (int32_t d = 0; d < n_dom; ++d)
-    if (f.act_of[(size_t)d] == 0) {
-      f.act_of[(size_t)d] = (int32_t)f.active.size();
-      f.active.push_back(d);
-    }
-  // the pairs dealt to their domains in ascending p (a counting sort)
+  domain_map_build(tree, parent, level, n_pairs, pair_domain, f.leaf_dom, f.act_of, f.active);
   const size_t A = f.active.size();
-  f.pair_start.assign(A + 1, 0);
-  for (int64_t p = 0; p < n_pairs; ++p) ++f.pair_start[(size_t)f.act_of[(size_t)pair_domain[p]] + 1];
-  for (size_t a = 0; a < A; ++a) f.pair_start[a + 1] += f.pair_start[a];
-  std::vector<int32_t> fill(f.pair_start.begin(), f.pair_start.end() - 1);
-  f.pairs.resize((size_t)n_pairs);
-  for (int64_t p = 0; p < n_pairs; ++p) f.pairs[(size_t)fill[(size_t)f.act_of[(size_t)pair_domain[p]]]++] = (int32_t)p;
+  csr_deal(A, n_pairs, [&](int64_t p) { return f.act_of[(size_t)pair_domain[p]]; }, nullptr, f.pair_start, f.pairs);
   // the units: each domain's range cut into runs of unit_pairs, the last one shorter
   f.unit_start.assign(A + 1, 0);
   for (size_t a = 0; a < A; ++a) {

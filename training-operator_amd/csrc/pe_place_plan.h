@@ -3,9 +3,7 @@
 // per call, and tests/cpp/test_place_plan.cc builds it under the sanitizers.
 //
 // The hierarchy is pe_gang_capacity_tree's (pe_tree_plan.h validates it).  For the call's `level` the plan holds
-//   leaf_dom[size[0]]   the level-`level` domain of leaf domain k, walked up the parent map; -1 = none
-//   act_of[size[level]] the ACTIVE index of a level-`level` domain (active = at least one job), -1 = inactive
-//   active[A]           the active domains' ids, ascending
+//   leaf_dom, act_of, active[A]   pe_domain_map.h's maps; a domain is active when it has at least one job
 //   job_start[A + 1], jobs[J]   CSR from active domain to its jobs in (priority desc, index asc) order
 //   pod_off[G + 1]      each group's first pod slot (groups in input order)
 // The batch arrays (offsets monotonic, counts >= 0) are the engine's to check before the plan is built.
@@ -13,9 +11,8 @@
 #define PE_PLACE_PLAN_H_
 
 #include <algorithm>
-#include <numeric>
 
-#include "pe_tree_plan.h"
+#include "pe_domain_map.h"
 
 namespace pe {
 
@@ -62,34 +59,14 @@ inline PlacePlanError place_plan_build(PlacePlan& plan, int64_t n_jobs, const in
   p.level = level;
   p.n_leaf = tree.size[0];
   p.n_dom = n_dom;
-  // leaf -> level: one step up the parent map per level
-  p.leaf_dom.resize((size_t)p.n_leaf);
-  std::iota(p.leaf_dom.begin(), p.leaf_dom.end(), 0);
-  for (int l = 0; l < level; ++l)
-    for (int32_t& d : p.leaf_dom)
-      if (d >= 0) d = parent[tree.off[l] + d];
-  // active domains, ascending
-  p.act_of.assign((size_t)n_dom, -1);
-  p.job_start.assign(1, 0);
-  for (int64_t j = 0; j < n_jobs; ++j) p.act_of[(size_t)job_domain[j]] = 0;
-  for (int32_t d = 0; d < n_dom; ++d)
-    if (p.act_of[(size_t)d] == 0) {
-      p.act_of[(size_t)d] = (int32_t)p.active.size();
-      p.active.push_back(d);
-    }
+  domain_map_build(tree, parent, level, n_jobs, job_domain, p.leaf_dom, p.act_of, p.active);
   // jobs by (priority desc, index asc), then dealt to their domains in that order
   std::vector<int32_t> order((size_t)n_jobs);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [priority](int32_t a, int32_t b) { return priority[a] > priority[b]; });
-  p.job_start.assign(p.active.size() + 1, 0);
-  for (int64_t j = 0; j < n_jobs; ++j) ++p.job_start[(size_t)p.act_of[(size_t)job_domain[j]] + 1];
-  for (size_t a = 0; a < p.active.size(); ++a) p.job_start[a + 1] += p.job_start[a];
-  std::vector<int32_t> fill(p.job_start.begin(), p.job_start.end() - 1);
-  p.jobs.resize((size_t)n_jobs);
-  for (int32_t j : order) p.jobs[(size_t)fill[(size_t)p.act_of[(size_t)job_domain[j]]]++] = j;
-  const int64_t G = n_jobs > 0 ? job_group_off[n_jobs] : 0;
-  p.pod_off.assign((size_t)G + 1, 0);
-  for (int64_t g = 0; g < G; ++g) p.pod_off[(size_t)g + 1] = p.pod_off[(size_t)g] + group_count[g];
+  csr_deal(p.active.size(), n_jobs, [&](int64_t j) { return p.act_of[(size_t)job_domain[j]]; }, order.data(),
+           p.job_start, p.jobs);
+  p.pod_off = pod_offsets(n_jobs > 0 ? job_group_off[n_jobs] : 0, group_count);
   plan = std::move(p);
   if (bad_index) *bad_index = -1;
   return PLACE_OK;
