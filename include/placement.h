@@ -287,17 +287,29 @@ int pe_pg_min_resources_wide(pe_ctx* ctx, int32_t mode, int64_t n_jobs, int32_t 
  * of this shard, device-resident.  The kernel picks the fastest exact path for the batch and the
  * device layout follows it (pe_fit_mask_layout):
  *   PE_MASK_NODE_TILES (compare paths): word (j, c) holds nodes 64c..64c+63 (bit n%64) at
- *     ((j / 16) * Wt + c / 4) * 64 + (j % 16) * 4 + c % 4,   Wt = ceil(words_per_row / 4)
+ *     ((j / 16) * Wt + c / 4) * 64 + (j % 16) * 4 + c % 4,   Wt = ceil(words_per_row / 4);
+ *     ceil(J / 16) * Wt * 64 words
  *   PE_MASK_JOB_BITS (dictionary-coded path): word (b, n) holds jobs 64b..64b+63 (bit j%64) for
- *     node n at b * S + n,  S = shard nodes rounded up to 512
- *   PE_MASK_ROWS (bit-plane path, default): row-major, word (j, c) at j * P + c, P =
- *     pe_fit_mask_row_pitch (a whole number of 8192-node blocks, >= ceil(S / 8192) * 128 words;
- *     S = shard nodes; padding bits 0)
+ *     node n at b * St + n,  St = shard nodes rounded up to 1024;  ceil(J / 64) * St words
+ *   PE_MASK_ROWS (bit-plane path, default, and the LDS digit-plane path): row-major, word (j, c) at
+ *     j * P + c;  J * P words.  The pitch P is whatever pe_fit_mask_row_pitch returns: at least
+ *     words_per_row and a whole number of 128-B lines (16 words) -- on the bit-plane path a whole number
+ *     of 8192-node blocks (128 words), on the LDS digit-plane path a whole number of that path's 2048-,
+ *     4096- or 8192-node blocks, which may be fewer words than one 8192-node block
  *   PE_MASK_NODE_BLOCKS (bit-plane path, fit_path_mask bit5): word (j, c) at
- *     ((c / 128) * J + j) * 128 + c % 128, i.e. per 8192-node block a [J][128]-word slab
- * All layouts are written as whole 128-B lines.  pe_fit_mask_rows always hands rows back
+ *     ((c / 128) * J + j) * 128 + c % 128, i.e. per 8192-node block a [J][128]-word slab;
+ *     ceil(S / 8192) * J * 128 words, S = shard nodes
+ * All layouts are written as whole 128-B lines, and every run writes every word of the extent stated
+ * above.  Padding inside it -- bits of nodes >= S, words the formulas address for no (job, node) pair, job
+ * bits >= J of PE_MASK_JOB_BITS -- is 0 in every layout, with two exceptions.  Rows J .. 16 * ceil(J / 16)
+ * - 1 of PE_MASK_NODE_TILES are unspecified: the job table is padded with a request that a node with
+ * INT64_MAX in every dimension and every label bit still fits.  With the study knob
+ * PE_ROW_PITCH_BLOCKS above its default the words of a PE_MASK_ROWS row past the last 8192-node block
+ * are unspecified (never written).  pe_fit_mask_rows always hands rows back
  * row-major [n_rows][words_per_row].  Counts are per job over this shard (sum across shards).
- * One-shot form: upload + compute + counts to host; *dev_mask receives the device pointer. */
+ * One-shot form: upload + compute + counts to host; *dev_mask receives the device pointer.  The
+ * pointer is valid until the next pe_fit_mask, pe_jobs_upload, pe_load_nodes or pe_destroy on the
+ * context, and every pe_fit_mask_run until then writes the same buffer. */
 int pe_fit_mask(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, const uint32_t* need,
                 int64_t* out_feasible_count, const uint64_t** dev_mask, int64_t* words_per_row);
 /* Staged form (device-resident inputs, used by the benchmark).  pe_jobs_upload (and pe_fit_mask)

@@ -186,7 +186,7 @@ constexpr int FC_JT = 64;       // coded fit: jobs per wave (one 64-bit word per
 hipError_t launch_encode_nodes(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
                                int64_t n_pad, CodeSpec spec, const int64_t* vals, const uint32_t* needs, uint32_t* X);
 // Coded-path mask layout (bits over jobs): word (b, n) = jobs 64b..64b+63 at node n (bit j%64),
-// stored at b * node_stride + n, node_stride = ceil(Ns/512)*512.
+// stored at b * node_stride + n, node_stride = ceil(Ns/1024)*1024 (whole wave tiles of FC_CH chunks).
 // therm = 0: jcode = C (ranks), k = ~M;   therm = 1: jcode = ~Y (one bit per field cleared), k unused
 hipError_t launch_fit_mask_coded(hipStream_t s, int therm, const uint32_t* X, int64_t Ns, int64_t node_stride,
                                  const uint32_t* jcode, uint32_t not_guard, int64_t J, int64_t tiles_per_wave,
@@ -222,7 +222,8 @@ hipError_t launch_fit_mask_planes(hipStream_t s, const uint32_t* planes, int64_t
 // (blk, r) takes jobs r, r+R, ...; u32 word w of row j at j * nblk * 256 + w.  jcode and counts are
 // phase-major: entry r * Jr + i belongs to job r + R * i (Jr = ceil(J / R) rounded up to 4), so
 // every wave reads and counts a contiguous run.
-// pitch_blk >= nblk: mask row pitch in 8192-node blocks (1 KiB each; words past nblk are not written)
+// pitch_blk >= nblk: mask row pitch in 8192-node blocks (1 KiB each).  pitch_blk > nblk only with the study knob
+// PE_ROW_PITCH_BLOCKS: the words past nblk are then not written (placement.h: unspecified)
 // unit_ctr (nblk zeroed counters, or nullptr): the waves of a block share its (phase, 64-job batch)
 // units through the block's counter instead of each taking its own phase -- same rows, same counts.
 hipError_t launch_fit_mask_planes_rows(hipStream_t s, const uint32_t* planes, int64_t nblk, const uint64_t* jcode,

@@ -348,11 +348,13 @@ class Engine:
         self.h = h
         self.rank, self.world_size = rank, world_size
         self.n_nodes = 0
+        self.mask_ptr = 0
 
     def close(self):
         if getattr(self, "h", None):
             self.lib.pe_destroy(self.h)
             self.h = None
+            self.mask_ptr = 0
 
     def __del__(self):
         try:
@@ -374,6 +376,7 @@ class Engine:
         isl = None if island is None else _c(island, np.int32)
         self._chk(self.lib.pe_load_nodes(self.h, n, _p(cap), _p(used), _p(lab), _p(isl)), "pe_load_nodes")
         self.n_nodes = n
+        self.mask_ptr = 0
 
     def update_nodes(self, slots, op, cap=None, used=None, labels=None, island=None):
         """pe_update_nodes: per entry op 0 (NODE_SET: cap[i][4], used[i][4], labels, island replace
@@ -490,6 +493,7 @@ class Engine:
         req = _c(req, np.int64).reshape(-1, 4)
         nd = None if need is None else _c(need, np.uint32)
         self.fit_jobs = req.shape[0]
+        self.mask_ptr = 0
         self._chk(self.lib.pe_jobs_upload(self.h, req.shape[0], _p(req), _p(nd)), "pe_jobs_upload")
 
     def fit_mask_run(self):
@@ -509,7 +513,37 @@ class Engine:
                                        ctypes.byref(wpr)), "pe_fit_mask")
         self.fit_jobs = req.shape[0]
         self.words_per_row = wpr.value
+        self.mask_ptr = int(dptr.value or 0)   # valid until the next fit_mask, jobs_upload, load_nodes or close
         return counts
+
+    def mask_extent(self) -> int:
+        """u64 words of the device mask that the current layout's formula addresses (include/placement.h)."""
+        b, e = self.shard_range()
+        J, S, layout = self.fit_jobs, e - b, self.fit_mask_layout()
+        Wn = (S + 63) // 64
+        if layout == _abi.PE_MASK_NODE_TILES:
+            return (J + 15) // 16 * ((Wn + 3) // 4) * 64
+        if layout == _abi.PE_MASK_JOB_BITS:
+            return (J + 63) // 64 * ((S + 1023) // 1024 * 1024)
+        if layout == _abi.PE_MASK_NODE_BLOCKS:
+            return (S + 8191) // 8192 * J * 128
+        return J * self.fit_mask_row_pitch()
+
+    def read_mask_words(self, n_words: int) -> np.ndarray:
+        """The first n_words u64 words at the device pointer the last fit_mask returned: pe_synchronize, then one
+        synchronous device-to-host copy.  At most mask_extent() words."""
+        if not self.mask_ptr:
+            raise PlacementError(_abi.PE_ESTATE, "read_mask_words: no device mask pointer held (fit_mask first)")
+        n = int(n_words)
+        if not 0 <= n <= self.mask_extent():
+            raise PlacementError(_abi.PE_EINVAL, f"read_mask_words: {n} words outside the layout's {self.mask_extent()}")
+        self.synchronize()
+        out = np.zeros(n, dtype=np.uint64)
+        if n:
+            rc = _abi.hip_memcpy()(_p(out), ctypes.c_void_p(self.mask_ptr), ctypes.c_size_t(8 * n), _abi.HIP_MEMCPY_D2H)
+            if rc != 0:
+                raise PlacementError(_abi.PE_EHIP, f"read_mask_words: hipMemcpy returned {rc}")
+        return out
 
     def fit_mask_layout(self) -> int:
         v = ctypes.c_int32()

@@ -31,6 +31,8 @@ PE_MAX_SPLIT_PARTS = 1024
 PE_SPLIT_TOO_MANY = -1
 PE_SLICE_NODE = -1
 PE_MAX_PAIR_VICTIMS = 64
+PE_MASK_NODE_TILES, PE_MASK_JOB_BITS, PE_MASK_NODE_BLOCKS, PE_MASK_ROWS = 0, 1, 2, 3
+HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
 ERR_NAMES = {PE_EINVAL: "PE_EINVAL", PE_EOVERFLOW: "PE_EOVERFLOW", PE_ENOMEM: "PE_ENOMEM", PE_EHIP: "PE_EHIP",
              PE_ERCCL: "PE_ERCCL", PE_ESTATE: "PE_ESTATE", PE_ENODEV: "PE_ENODEV"}
@@ -147,3 +149,18 @@ def load(path: str = LIB_PATH):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+_hip_memcpy = None
+
+
+def hip_memcpy():
+    """hipMemcpy of the HIP runtime libplacement.so is linked against: looked up through the library's own handle,
+    which searches the library and then its dependencies -- the process keeps one runtime, whatever else is loaded."""
+    global _hip_memcpy
+    if _hip_memcpy is None:
+        fn = load().hipMemcpy
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        _hip_memcpy = fn
+    return _hip_memcpy
