@@ -377,7 +377,7 @@ hipError_t launch_walk_prep(hipStream_t s, const int64_t* res, int64_t stride, i
 // join nx's overlay with their current state.
 hipError_t launch_walk_switch(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
                               const uint32_t* slow, const WalkIndex& nx);
-// hipcub radix sort of n u64 keys (temp == nullptr: *temp_bytes = the scratch size needed).
+// rocPRIM radix sort of n u64 keys (temp == nullptr: *temp_bytes = the scratch size needed).
 hipError_t sort_keys_u64(void* temp, size_t* temp_bytes, const uint64_t* in, uint64_t* out, int64_t n, hipStream_t s);
 // Sorted SoA copy, pos[], round summaries from the sorted keys w.sk.
 hipError_t launch_walk_build(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
