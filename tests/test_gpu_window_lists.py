@@ -5,6 +5,7 @@ call's first window; every list of it must be TIGHT against scan_emulator.keys o
 and the limit exact (window_lists.expected_lists; the contract is stated in cand_lists.py).  The end-to-end suites
 compare placements, which a list that is merely sound -- too short, its limit too low -- never changes."""
 import os
+import time
 
 import numpy as np
 import pytest
@@ -82,4 +83,22 @@ def test_first_window_lists_are_tight(mode, tmp_path, monkeypatch):
     if not scan:
         # a call that rescans runs more than one window and its counters cannot be told apart: at least half of
         # the calls the model names must have been counted
+        assert tally["overlay"] >= need.overlay // 2 and tally["rebuilt"] >= need.lists // 2, (tally, need)
+
+
+@pytest.mark.parametrize("mode", sorted(wl.MODES))
+def test_first_window_lists_are_tight_at_key_edges(mode, tmp_path, monkeypatch):
+    """EDGE_CONFIGS: low bits in residuals and requests, so that keys borrow and K(n) order is not key order (the
+    walk's stop bound, its start round, fast_key's carry into the high word, the low parts apply and the scatter
+    keep), and nodes and requests on node_prep's and s(q)'s saturation lines.  test_window_lists_cpu.py shows on
+    the model alone that a walk with less slack, and nothing in CONFIGS, fails exactly here."""
+    tally = dict(lists=0, full=0, short=0, empty=0, overlay=0, rebuilt=0)
+    t0 = time.perf_counter()
+    for cfg in wl.EDGE_CONFIGS:
+        walk_config(mode, cfg, tmp_path, monkeypatch, tally)
+    print(mode, tally, "%.2f s" % (time.perf_counter() - t0))
+    scan = mode in wl.SCAN_MODES
+    need = wl.edge_totals(scan)
+    assert (tally["lists"], tally["full"], tally["short"], tally["empty"]) == need[:4], (tally, need)
+    if not scan:
         assert tally["overlay"] >= need.overlay // 2 and tally["rebuilt"] >= need.lists // 2, (tally, need)
