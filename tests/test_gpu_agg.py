@@ -8,8 +8,10 @@ import numpy as np
 import pytest
 
 import oracle
+from agg_batches import concat as _concat   # (the builders live in agg_batches.py; other test modules
+from agg_batches import one_job_csr as _one_job_csr   # import them from here under these names)
+from agg_batches import random_csr, random_keys_csr   # noqa: F401
 from placement import V1, V2, Engine
-from test_gpu_parity import random_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -42,36 +44,6 @@ def test_agg_segment_jobs_override(eng, monkeypatch, seg_jobs):
     monkeypatch.setenv("PE_AGG_SEG_JOBS", seg_jobs)
     for J in (1, 300, 9000, 40000):   # (40000: the chunked multi-thread path, staging sized from a bound)
         _check(eng, V1, random_csr(J, 700 + J))
-
-
-def _one_job_csr(n_groups, n_cont_per_group, seed):
-    rng = np.random.default_rng(seed)
-    jgo = np.array([0, n_groups], np.int32)
-    rep = rng.integers(-1, 5, n_groups).astype(np.int32)
-    gco = (np.arange(n_groups + 1) * n_cont_per_group).astype(np.int32)
-    C = int(gco[-1])
-    req = rng.integers(0, 2**30, (C, 4), dtype=np.int64)
-    fl = (rng.integers(0, 16, C) | (rng.integers(0, 4, C) << 4)).astype(np.uint8)
-    mm = np.array([int(rep.clip(0).sum()) // 2 + 1], np.int32)
-    return jgo, mm, rep, gco, req, fl
-
-
-def _concat(parts):
-    """CSR batches back to back."""
-    jgo, mm, rep, gco, req, fl = [np.zeros(1, np.int32)], [], [], [np.zeros(1, np.int32)], [], []
-    g_off = c_off = 0
-    for p in parts:
-        jgo.append(p[0][1:] + g_off)
-        mm.append(p[1])
-        rep.append(p[2])
-        gco.append(p[3][1:] + c_off)
-        req.append(p[4].reshape(-1, 4))
-        fl.append(p[5])
-        g_off += int(p[0][-1])
-        c_off += int(p[3][-1])
-    return (np.concatenate(jgo).astype(np.int32), np.concatenate(mm).astype(np.int32),
-            np.concatenate(rep).astype(np.int32), np.concatenate(gco).astype(np.int32),
-            np.concatenate(req).astype(np.int64), np.concatenate(fl).astype(np.uint8))
 
 
 @pytest.mark.parametrize("mode", [V1, V2])
@@ -146,20 +118,6 @@ def test_agg_resync_batch_equals_per_object_calls(eng, mode):
 
 
 # ------------------------------------------------------------------ key tables (ABI 7)
-
-def random_keys_csr(J, n_keys, seed, big=False):
-    """random_csr's structure with n_keys values per container and u32 flags (presence bits of the
-    n_keys keys | kind << 16)."""
-    jgo, mm, rep, gco, _, fl8 = random_csr(J, seed, big)
-    rng = np.random.default_rng(seed + 1)
-    C = int(gco[-1])
-    hi = 2**62 if big else 2**40
-    req = rng.integers(0, hi, (C, n_keys), dtype=np.int64)
-    req[rng.random((C, n_keys)) < 0.3] = 0
-    pres = rng.integers(0, 1 << n_keys, C, dtype=np.int64).astype(np.uint32)
-    fl = pres | ((fl8.astype(np.uint32) >> 4) << 16)
-    return jgo, mm, rep, gco, req, fl
-
 
 def _check_keys(eng, mode, arrs):
     got = eng.pg_min_resources_keys(mode, *arrs)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
+from agg_batches import random_csr   # noqa: F401  (also imported from here by other test modules)
 from oracle import flatten as F
 from oracle import semantics as S
 from placement import Engine, V1, V2, synth
@@ -76,24 +77,6 @@ def test_pg_min_resources_v2_golden(eng, golden_dir):
         assert F.unflatten(out[j], pres[j], GPU) == want, case["name"]
         assert mem[j] == case["want"]["minMember"]
         assert ovf[j] == 0
-
-
-def random_csr(J, seed, big=False):
-    rng = np.random.default_rng(seed)
-    ng = rng.integers(0, 5, J)
-    jgo = np.concatenate([[0], np.cumsum(ng)]).astype(np.int32)
-    G = int(jgo[-1])
-    rep = rng.integers(-1, 40, G).astype(np.int32)
-    rep[rng.random(G) < 0.05] = 2**31 - 1
-    nc = rng.integers(0, 5, G)
-    gco = np.concatenate([[0], np.cumsum(nc)]).astype(np.int32)
-    C = int(gco[-1])
-    hi = 2**62 if big else 2**40
-    req = rng.integers(0, hi, (C, 4), dtype=np.int64)
-    req[rng.random((C, 4)) < 0.3] = 0
-    fl = (rng.integers(0, 16, C) | (rng.integers(0, 4, C) << 4)).astype(np.uint8)
-    mm = rng.integers(-2, 60, J).astype(np.int32)
-    return jgo, mm, rep, gco, req, fl
 
 
 @pytest.mark.parametrize("mode", [V1, V2])
