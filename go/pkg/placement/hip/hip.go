@@ -613,6 +613,72 @@ func (e *Engine) GangCapacity(req []int64, need []uint32) (slots []int64, maxNod
 	return slots, maxNode, nodes, e.err(rc, "pe_gang_capacity")
 }
 
+// Signatures of FitExplain (PE_EXPLAIN_*).
+const (
+	ExplainBins   = 32 // one per 5-bit signature
+	ExplainLabels = 4  // signature bit of the label test
+	ExplainAny    = -1 // a jobDomain entry: the whole shard for that job
+)
+
+// ExplainNames are the resource names Message uses by default.
+var ExplainNames = [Dims]string{"cpu", "memory", "amd.com/gpu", "ephemeral-storage"}
+
+// FitExplanation is FitExplain's answer.
+type FitExplanation struct {
+	Hist []int64  // [J][32]: live nodes in job j's scope per signature (bit d: req_d > res_d, bit 4: labels)
+	Near []uint64 // [J][4]: the smallest shortfall among the nodes failing on dimension d alone, 0 = none; nil if not asked for
+}
+
+// Message is job j's histogram in kube-scheduler's manner: "{fits}/{live} nodes are available: {c} Insufficient
+// {name}, ..., {c} node(s) didn't match the required labels."  Reasons in the order cpu, memory, gpu, ephemeral,
+// labels with inclusive counts; zero counts are left out; with no reason the text ends after "available.".
+func (x *FitExplanation) Message(j int, names [Dims]string) string {
+	h := x.Hist[j*ExplainBins : (j+1)*ExplainBins]
+	var incl [5]int64
+	var live int64
+	for s, c := range h {
+		live += c
+		for r := 0; r < 5; r++ {
+			if s>>r&1 == 1 {
+				incl[r] += c
+			}
+		}
+	}
+	msg := fmt.Sprintf("%d/%d nodes are available", h[0], live)
+	sep := ": "
+	for d := 0; d < Dims; d++ {
+		if incl[d] != 0 {
+			msg += fmt.Sprintf("%s%d Insufficient %s", sep, incl[d], names[d])
+			sep = ", "
+		}
+	}
+	if incl[ExplainLabels] != 0 {
+		msg += fmt.Sprintf("%s%d node(s) didn't match the required labels", sep, incl[ExplainLabels])
+	}
+	return msg + "."
+}
+
+// FitExplain answers why job j's shape (req [J][4], need [J] or nil) fits no node: per job the shard's live nodes
+// counted by signature and, with near, per dimension the nearest miss.  jobDomain ([J] or nil = the whole shard;
+// ExplainAny = the whole shard for that job) restricts job j to one domain of `level` in the hierarchy levelSize /
+// parent, as for PlaceGreedyDomains.  Read-only.  Sharded: add the histograms over the shards and take the minimum
+// of the non-zero near values.
+func (e *Engine) FitExplain(req []int64, need []uint32, jobDomain []int32, level int32, levelSize, parent []int32, near bool) (*FitExplanation, error) {
+	J := len(req) / Dims
+	if need != nil && len(need) != J {
+		return nil, fmt.Errorf("FitExplain: %d needs for %d jobs", len(need), J)
+	}
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, fmt.Errorf("FitExplain: %d domains for %d jobs", len(jobDomain), J)
+	}
+	out := &FitExplanation{Hist: make([]int64, J*ExplainBins)}
+	if near {
+		out.Near = make([]uint64, J*Dims)
+	}
+	rc := C.pe_fit_explain(e.ctx, C.int64_t(J), ptr64(req), ptru32(need), ptr32(jobDomain), C.int32_t(level), C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr64(out.Hist), ptru64(out.Near))
+	return out, e.err(rc, "pe_fit_explain")
+}
+
 // DomainCapacity is GangCapacityDomains' answer; a part that was not asked for is nil.
 type DomainCapacity struct {
 	DomSlots    []int64 // [J][nDomains]: pods of job j's shape that domain k holds

@@ -854,6 +854,58 @@ int pe_assume_gangs(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off 
                     const int32_t* pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
                     int64_t* out_pods /* or NULL */);
 
+/* (ABI 7, additive) Why a pod shape fits no node, counted per reason: the numbers behind the Unschedulable
+ * condition a gang scheduler owes its users on the PodGroup and the job -- kube-scheduler's "0/5000 nodes are
+ * available: 3200 Insufficient amd.com/gpu, 1800 node(s) didn't match ..." -- and behind the two decisions
+ * that follow a "no": preemption helps only on nodes that fail on resources alone, and a scale-up is sized by
+ * how much the nearest miss lacks.  NO reference function, as all of fit and placement.  Read-only.
+ * With residuals, labels and removed slots exactly as pe_fit_mask sees them now, the SIGNATURE of (job j,
+ * node n) is a 5-bit value:
+ *   bit d (d = 0 .. 3)          set iff req[j][d] > res[n][d]  (signed int64: a zero request is still
+ *                               insufficient on a negative residual; the negation of fit's req_d <= res_d)
+ *   bit 4 (PE_EXPLAIN_LABELS)   set iff (labels[n] & need[j]) != need[j]  (bit 31 is the engine's island bit,
+ *                               matched like any label bit)
+ * Signature 0 is fit(j, n).  A node is LIVE iff its slot is not removed and it lies in this shard; removed
+ * slots and padding count nowhere.
+ *   out_hist[j][s], s in 0 .. 31 = the live nodes in job j's scope with signature s
+ *   out_near[j][d]               = min over the live nodes in scope whose signature is exactly 1 << d of
+ *                                  req[j][d] - res[n][d], as an exact unsigned 64-bit value in [1, 2^64 - 2]
+ *                                  (a residual of -(2^63 - 1) against a request of 2^63 - 1 does not wrap);
+ *                                  0 when there is no such node
+ * Scope: job_domain NULL -- every live node of the shard, with or without an island.  Otherwise level,
+ * n_levels, level_size, parent and dom_level(n) mean exactly what they mean in pe_place_greedy_domains, and job
+ * j counts only the nodes with dom_level(n) == job_domain[j]; job_domain[j] == PE_EXPLAIN_ANY is the whole
+ * shard for that job.  Nothing of the hierarchy is kept in the context.
+ * Worked example: the job (4000 m cpu, 64 Gi memory, 8 GPUs, 0 ephemeral) with need = bit 0, and the nodes, as
+ * free (cpu, memory Gi, GPUs): n0 (8000, 128, 8) with bit 0 -> 0; n1 (8000, 128, 4) with bit 0 -> 4; n2 (2000,
+ * 32, 0) with bit 0 -> 7; n3 (8000, 128, 8) without labels -> 16; n4 (8000, 128, 6) with bit 0 -> 4; n5 removed
+ * -> not counted.  out_hist = {0: 1, 4: 2, 7: 1, 16: 1}, 5 live nodes, out_near = {0, 0, 2, 0}; inclusive
+ * counts: cpu 1, memory 1, gpu 3, ephemeral 0, labels 1 -- "1/5 nodes are available: 1 Insufficient cpu, 1
+ * Insufficient memory, 3 Insufficient amd.com/gpu, 1 node(s) didn't match the required labels."
+ * Identities:
+ *   - out_hist[j][0] is pe_fit_mask's count and pe_gang_capacity's out_nodes for the same row;
+ *   - the sum over s of out_hist[j][s] is the number of live nodes in scope;
+ *   - the INCLUSIVE count of reason r is the sum over the s with bit r set: a node lacking cpu and gpu counts
+ *     under both, as kube-scheduler reports it; bin 1 << d holds the nodes that fail on dimension d ALONE;
+ *   - the domain form summed over every domain of a level, plus the nodes in no domain of that level, is the
+ *     unrestricted form.
+ * Sharded contexts: the call works with world_size > 1; the tables are per shard, like pe_gang_capacity's
+ * counts.  The caller adds the histograms and takes the minimum of the non-zero near values.
+ * The device residuals, the host mirror, the reset snapshot, the staged fit-mask state and pe_stats are
+ * untouched.  need NULL = 0; each out_* may be NULL (without out_near the near values are not computed).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): n_jobs < 0; a
+ * negative request; and with job_domain given: everything pe_gang_capacity_tree refuses about the hierarchy,
+ * level outside [0, n_levels), a job_domain outside [-1, level_size[level]).  With job_domain NULL the four
+ * hierarchy arguments are not read.  PE_ESTATE: a call before pe_load_nodes.  n_jobs == 0, an empty shard and
+ * a domain without nodes are PE_OK with zeros. */
+#define PE_EXPLAIN_BINS 32
+#define PE_EXPLAIN_LABELS 4   /* signature bit of the label test */
+#define PE_EXPLAIN_ANY (-1)
+int pe_fit_explain(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, const uint32_t* need /* or NULL = 0 */,
+                   const int32_t* job_domain /*[j] or NULL = whole shard*/, int32_t level, int32_t n_levels,
+                   const int32_t* level_size, const int32_t* parent,
+                   int64_t* out_hist /*[j][32] or NULL*/, uint64_t* out_near /*[j][4] or NULL*/);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "pe_explain_plan.h"
 #include "pe_hostx.h"
 #include "pe_kernels.h"
 #include "pe_ledger_plan.h"
@@ -395,6 +396,16 @@ struct pe_ctx {
   std::vector<uint64_t> lv_pkeys;          // the call's distinct (shape, count, max_level), packed
   std::vector<int32_t> lv_ptab, lv_pof;    // their dedupe table, each job's pick
   pe::SlicePlan sl_plan;                   // pe_gang_slice_tree: the call's rows and picks (its buffers are cp_* and lv_*)
+  // why a shape fits no node (pe_fit_explain, pe_engine_explain.cpp): the call's distinct (request, need, domain)
+  // records, their dedupe table and each job's record, the leaf -> level-domain map; one block in (the records, then
+  // the map), one launch's tables on the device ([chunk][32] counts, then [chunk][4] near values) and every
+  // launch's tables on their way out.  Grow and are reused; nothing outlives a call.
+  std::vector<pe::ExplainRec> ex_uniq;
+  std::vector<int32_t> ex_tab, ex_of, ex_leaf;
+  HostBuf<uint8_t> ex_hin;
+  DevBuf<uint8_t> ex_in;
+  DevBuf<uint64_t> ex_out;
+  HostBuf<uint64_t> ex_hout;
   // the domain calls (pe_place_greedy_domains and pe_place_min_member_domains, pe_engine_place.cpp;
   // pe_gang_fit_domains, pe_engine_fit.cpp; pe_place_first_fit_domains, pe_engine_first_fit.cpp;
   // pe_gang_preempt_domains, pe_engine_preempt.cpp; their shared host path: pe_domain_call.h).  One set for all of
@@ -503,6 +514,7 @@ struct pe_ctx {
     dm_hin.release(); dm_in.release(); dm_out.release(); dm_hout.release(); dm_log.release(); dm_dom.release();
     dm_seg.release(); dm_segw.release(); dm_hoff.release(); dm_hlarge.release(); dm_large.release(); dm_scratch.release();
     pp_place.release(); ff_state.release(); ff_hopen.release();
+    ex_hin.release(); ex_in.release(); ex_out.release(); ex_hout.release();
     ld_hin.release(); ld_in.release();
     if (dm_ev) (void)hipEventDestroy(dm_ev);
     for (hipEvent_t e : cp_ev)

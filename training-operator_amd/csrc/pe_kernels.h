@@ -468,6 +468,17 @@ static_assert(sizeof(CapAcc) == 16, "CapAcc must be 16 B");
 hipError_t launch_gang_capacity(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels, int64_t Ns,
                                 const CapShape* shapes, int64_t S, CapAcc* partials, CapAcc* out);
 
+// ---- why a shape fits no node (pe_fit_explain, pe_explain.hip; records and chunking: pe_explain_plan.h)
+constexpr int EX_TS = 32;                        // records between two block folds
+struct ExplainRec;
+// hist[S][32] += per record the shard's live nodes in the record's scope by 5-bit signature, near[S][4] = min per
+// dimension d over the nodes with signature 1 << d of req_d - res_d as u64 (near NULL: not computed).  The caller
+// zeroes hist and fills near with ~0 (no such node).  leaf_dom[n_leaf] (pe_explain_plan.h explain_leaf_dom) is
+// read only when with_domains: without it every record counts the whole shard.
+hipError_t launch_fit_explain(hipStream_t s, const int64_t* res, int64_t stride, const uint32_t* labels,
+                              const int32_t* island, int64_t Ns, const int32_t* leaf_dom, int n_leaf, bool with_domains,
+                              const ExplainRec* recs, int64_t S, uint64_t* hist, uint64_t* near);
+
 // ---- gang capacity per topology domain: the leaf table of both table calls (pe_domains.hip)
 constexpr int DM_MAX_DOMAINS = 65536;            // PE_MAX_DOMAINS
 // dom_slots / dom_nodes [S][n_domains] += over the shard's Ns nodes (the caller zeroes them; dom_nodes may be

@@ -25,7 +25,8 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
-           "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE"]
+           "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
+           "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY"]
 
 
 class PlacementError(RuntimeError):
@@ -69,6 +70,57 @@ def wide_limbs(values):
         fl[i] = x & (2**64 - 1)
         fh[i] = x >> 64
     return lo, hi
+
+
+PE_EXPLAIN_BINS = 32
+PE_EXPLAIN_LABELS = 4   # signature bit of the label test
+PE_EXPLAIN_ANY = -1
+EXPLAIN_NAMES = ("cpu", "memory", "amd.com/gpu", "ephemeral-storage")
+
+
+def explain_message(hist_row, names=EXPLAIN_NAMES) -> str:
+    """One job's histogram ([32], ints) in kube-scheduler's manner: "{fits}/{live} nodes are available: {c}
+    Insufficient {name}, ..., {c} node(s) didn't match the required labels."  Reasons in the order cpu, memory,
+    gpu, ephemeral, labels with INCLUSIVE counts; zero counts are left out; with no reason the text ends after
+    "available."."""
+    h = [int(v) for v in hist_row]
+    incl = [sum(h[s] for s in range(PE_EXPLAIN_BINS) if s >> r & 1) for r in range(5)]
+    parts = [f"{incl[d]} Insufficient {names[d]}" for d in range(4) if incl[d]]
+    if incl[PE_EXPLAIN_LABELS]:
+        parts.append(f"{incl[PE_EXPLAIN_LABELS]} node(s) didn't match the required labels")
+    head = f"{h[0]}/{sum(h)} nodes are available"
+    return head + (": " + ", ".join(parts) + "." if parts else ".")
+
+
+class FitExplain(NamedTuple):
+    """Engine.fit_explain's answer.  hist int64 [J][32]: live nodes in scope per signature; near uint64 [J][4] or
+    None: the smallest shortfall among the nodes failing on dimension d alone, 0 = no such node."""
+    hist: np.ndarray
+    near: Optional[np.ndarray]
+
+    @property
+    def fits(self) -> np.ndarray:             # [J]: pe_fit_mask's count
+        return self.hist[:, 0]
+
+    @property
+    def live(self) -> np.ndarray:             # [J]: live nodes in scope
+        return self.hist.sum(axis=1)
+
+    @property
+    def insufficient(self) -> np.ndarray:     # [J][4]: nodes lacking dimension d, alone or not
+        bits = np.arange(PE_EXPLAIN_BINS)
+        return np.stack([self.hist[:, (bits >> d & 1) == 1].sum(axis=1) for d in range(4)], axis=1)
+
+    @property
+    def label_mismatch(self) -> np.ndarray:   # [J]
+        return self.hist[:, PE_EXPLAIN_BINS // 2:].sum(axis=1)
+
+    @property
+    def only(self) -> np.ndarray:             # [J][4]: nodes failing on dimension d alone
+        return self.hist[:, [1, 2, 4, 8]]
+
+    def message(self, j, names=EXPLAIN_NAMES) -> str:
+        return explain_message(self.hist[j], names)
 
 
 class DomainCapacity(NamedTuple):
@@ -579,6 +631,33 @@ class Engine:
         self._chk(self.lib.pe_gang_capacity(self.h, J, _p(req), _p(nd), _p(slots), _p(max_node), _p(nodes)),
                   "pe_gang_capacity")
         return slots, max_node, nodes
+
+    def fit_explain(self, req, need=None, job_domain=None, level=0, level_size=None, parent=None,
+                    near=True) -> "FitExplain":
+        """pe_fit_explain: why job j's shape (req [J][4], need [J] or None) fits no node -- per job the shard's
+        live nodes counted by 5-bit signature (bit d: req_d > res_d, bit 4: labels) and, with near=True, per
+        dimension the smallest shortfall among the nodes that fail on that dimension alone.  job_domain ([J] or
+        None = the whole shard; PE_EXPLAIN_ANY = the whole shard for that job) restricts job j to one domain of
+        `level` in the hierarchy level_size / parent, exactly as for place_greedy_domains.  Works on a sharded
+        context: add the shards' hist and take the minimum of the non-zero near values.  Read-only."""
+        req = _c(req, np.int64).reshape(-1, 4)
+        nd = None if need is None else _c(need, np.uint32)
+        J = req.shape[0]
+        if nd is not None and nd.shape != (J,):
+            raise ValueError("need must be [J]")
+        jd = None if job_domain is None else _c(job_domain, np.int32)
+        if jd is not None and jd.shape != (J,):
+            raise ValueError("job_domain must be [J]")
+        ls = None if level_size is None else _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        if jd is not None and ls is None:
+            raise ValueError("job_domain needs level_size")
+        hist = np.zeros((J, PE_EXPLAIN_BINS), dtype=np.int64)
+        nv = np.zeros((J, 4), dtype=np.uint64) if near else None
+        self._chk(self.lib.pe_fit_explain(self.h, J, _p(req), _p(nd), _p(jd), int(level), 0 if ls is None else len(ls),
+                                          _p(ls), _p(par), _p(hist), _p(nv)),
+                  "pe_fit_explain")
+        return FitExplain(hist, nv)
 
     def gang_capacity_domains(self, req, need=None, count=None, n_domains=None, tables=True) -> DomainCapacity:
         """pe_gang_capacity_domains: gang capacity per topology domain, the domain of a node being its

@@ -92,6 +92,7 @@ SIGNATURES = {
     "pe_gang_capacity_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, P, P, P, P, P, P]),
     "pe_gang_split_tree": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P]),
     "pe_gang_slice_tree": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P, P]),
+    "pe_fit_explain": (ctypes.c_int, [P, i64, P, P, P, i32, i32, P, P, P, P]),
     "pe_jobs_upload": (ctypes.c_int, [P, i64, P, P]),
     "pe_fit_mask_run": (ctypes.c_int, [P]),
     "pe_fit_counts": (ctypes.c_int, [P, P]),
