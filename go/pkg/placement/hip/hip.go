@@ -1078,6 +1078,34 @@ func (e *Engine) AssumeGangs(v *Victims) (pods int64, err error) {
 	return int64(n), e.err(rc, "pe_assume_gangs")
 }
 
+// DrainFitDomains answers, for every candidate c, whether the pods that the book of placed gangs v has on node
+// candNode[c] would all find a node in the level-`level` domain candDomain[c] with the node itself taken out, and
+// where (pe_drain_fit_domains).  groupNeed ([VG], nil = 0) holds the groups' required label bits: a move respects
+// labels.  fits[c] is 1 or 0, moved[c] the pods that had found a node when the rule stopped, failSlot[c] -1 or the
+// pod slot of the first pod that found no node, target[s] the node the pod of slot s moves to, or -1.  Read-only: a
+// caller acts on the answer with ReleaseGangs of the node's slots and AssumeGangs of the same groups at the targets.
+// withTargets false leaves target nil (it never crosses).  levelSize and parent describe the hierarchy exactly as for
+// GangCapacityTree.  A sharded engine refuses the call.
+func (e *Engine) DrainFitDomains(v *Victims, groupNeed []uint32, candNode, candDomain []int32, level int32, levelSize, parent []int32, withTargets bool) (fits []uint8, moved, failSlot []int64, target []int32, err error) {
+	nc := len(candNode)
+	if len(candDomain) != nc {
+		return nil, nil, nil, nil, fmt.Errorf("DrainFitDomains: %d nodes for %d domains", nc, len(candDomain))
+	}
+	if groupNeed != nil && len(groupNeed) != len(v.GroupCount) {
+		return nil, nil, nil, nil, fmt.Errorf("DrainFitDomains: %d needs for %d groups", len(groupNeed), len(v.GroupCount))
+	}
+	fits = make([]uint8, nc)
+	moved = make([]int64, nc)
+	failSlot = make([]int64, nc)
+	if withTargets {
+		target = make([]int32, len(v.PodNode))
+	}
+	rc := C.pe_drain_fit_domains(e.ctx, C.int64_t(len(v.GroupOff)-1), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq),
+		ptru32(groupNeed), ptr32(v.PodNode), C.int64_t(nc), ptr32(candNode), ptr32(candDomain), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr8(fits), ptr64(moved), ptr64(failSlot), ptr32(target))
+	return fits, moved, failSlot, target, e.err(rc, "pe_drain_fit_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

@@ -906,6 +906,68 @@ int pe_fit_explain(pe_ctx* ctx, int64_t n_jobs, const int64_t* req /*[j][4]*/, c
                    const int32_t* level_size, const int32_t* parent,
                    int64_t* out_hist /*[j][32] or NULL*/, uint64_t* out_near /*[j][4] or NULL*/);
 
+/* (ABI 7, additive) Can a node's pods move elsewhere, and where: the question about pods that are already
+ * placed.  Maintenance (cordon and drain before a firmware update: which of these nodes can go now without
+ * killing a gang?), defragmentation (free whole nodes by moving the small pods that sit on them) and a node hot
+ * swap (a replacement inside the same rack) all ask it, and without this call the only way to learn the answer
+ * is to remove the node, place its pods and reload.  NO reference function, as pe_gang_fit_domains.  Read-only.
+ * The residents are placed gangs in exactly the shape pe_release_gangs takes -- gang v has the groups
+ * [gang_group_off[v], gang_group_off[v + 1]) with group_count and group_req, pod_node holds the GLOBAL node id of
+ * every pod slot, groups in input order, -1 = slot skipped; S = the sum of the counts -- plus the groups' need: a
+ * move respects labels, which a release never looks at.  A caller may hand over its whole book of placed gangs;
+ * slots on nodes that are no candidate are ignored.  Levels, level_size, parent and dom_level(n) mean exactly what
+ * they mean in pe_place_greedy_domains; nothing is kept in the context; one call has one level.
+ * Candidate c, with n = cand_node[c] and D = cand_domain[c], is judged alone against the CURRENT residuals:
+ *   Evicted pods   the pod slots s with pod_node[s] == n, in ascending s: gang order, group order, slot order.
+ *   Runs           consecutive evicted slots of one group form a RUN of r pods of that group's request and need:
+ *                  the pods of a group are identical, so the run is a group of count r.  A run of a group whose
+ *                  need has PE_NEED_ISLAND moves as one unit of r x request onto one node (a product that
+ *                  overflows fits nowhere): the island group of every placement call.
+ *   The move       the answer is what pe_place_greedy_domains would give for the single job whose groups are the
+ *                  runs in that order, with job_domain = D, on an inventory in which slot n is a removed slot and
+ *                  every other node has its current residual.  Node n is out of every decision, whether or not
+ *                  it lies in D, and nothing is given back to it: it is gone.  D need not be n's own domain:
+ *                  "into the same rack" is D = n's rack, "out of this rack" is another one.
+ * A candidate that is itself a removed slot: its pods count nothing (the ledger's rule); it fits with 0 pods.
+ *   out_fits[c]      = 1 or 0
+ *   out_moved[c]     = the pods that had found a node when the rule stopped: all of them when the candidate fits;
+ *                      a failing island run contributes 0
+ *   out_fail_slot[c] = -1 when it fits, else the slot index, in pod_node, of the first pod that found no node
+ *                      (for an island run, the run's first slot)
+ *   out_target[s]    = for every slot of the call: the GLOBAL node the pod of slot s moves to when its node is a
+ *                      candidate that fits, -1 otherwise (slots on non-candidates, slots holding -1, slots on
+ *                      removed nodes and every slot of a candidate that does not fit); every cell is written
+ * A candidate without pods fits with 0 pods; a domain with no node other than n holds only a candidate without
+ * pods.  n_cands == 0 and n_gangs == 0 are PE_OK, with every out_target -1.  Each out_* may be NULL; group_need
+ * NULL = 0.
+ * Worked example: one rack holds A, B and C; B has 3 free GPUs and C has 4, cpu and memory equal and ample.  A
+ * holds three pods in slot order: two of one group of 2 GPUs each, then one of another group with 3 GPUs.  Drain
+ * A: the first 2-GPU pod takes B (the best fit, 1 left), the second takes C (2 left), the 3-GPU pod finds
+ * nothing -- fits 0, moved 2, fail_slot 2, all targets -1.  With the 3-GPU gang first in the book it takes B and
+ * the two 2-GPU pods take C -- fits 1, moved 3, targets (B, C, C).  The answer is the greedy rule's in the
+ * caller's slot order, not a bin-packing optimum: the caller orders the book.
+ * Acting on the answer: pe_release_gangs of the candidate's slots, then pe_assume_gangs of the same groups with
+ * pod_node = the targets.  Two candidates of one call may have been given the same free slots: act on one, then
+ * ask again.
+ * Read-only: the device residuals, the host mirror, the reset snapshot, labels and islands, the staged fit batch
+ * and pe_stats are left exactly as they are.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one): everything
+ * pe_release_gangs refuses about offsets, counts, requests and pod_node; more than 2^31 - 1 pod slots; n_cands
+ * outside [0, 2^31 - 1); a NULL cand_node or cand_domain with n_cands > 0; a cand_node outside [0, n_total); the
+ * same node twice in cand_node (one target per slot is only defined then; several target domains for one node
+ * are several calls); everything pe_gang_fit_domains refuses about the hierarchy and level; a cand_domain outside
+ * [0, level_size[level]).  PE_ESTATE: a call before pe_load_nodes.  PE_ENOMEM: as pe_gang_fit_domains. */
+int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off /*[V+1]*/,
+                         const int32_t* group_count /*[VG]*/, const int64_t* group_req /*[VG][4]*/,
+                         const uint32_t* group_need /*[VG] or NULL = 0*/,
+                         const int32_t* pod_node /*[S]: global node id per pod slot, -1 = skipped*/,
+                         int64_t n_cands, const int32_t* cand_node /*[C]*/, const int32_t* cand_domain /*[C]*/,
+                         int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                         const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                         uint8_t* out_fits /*[C] or NULL*/, int64_t* out_moved /*[C] or NULL*/,
+                         int64_t* out_fail_slot /*[C] or NULL*/, int32_t* out_target /*[S] or NULL*/);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

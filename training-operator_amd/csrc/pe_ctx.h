@@ -1,6 +1,6 @@
 // libplacement internals shared by the engine's units (pe_engine.cpp, pe_engine_greedy.cpp,
 // pe_engine_capacity.cpp, pe_domain_call.cpp, pe_engine_place.cpp, pe_engine_fit.cpp, pe_engine_first_fit.cpp,
-// pe_engine_preempt.cpp, pe_engine_ledger.cpp): device and pinned buffers, the helper threads, error mapping, input
+// pe_engine_preempt.cpp, pe_engine_ledger.cpp, pe_engine_drain.cpp): device and pinned buffers, the helper threads, error mapping, input
 // checks and the context itself.  Not part of the ABI.
 #pragma once
 
@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "pe_drain_plan.h"
 #include "pe_explain_plan.h"
 #include "pe_hostx.h"
 #include "pe_kernels.h"
@@ -438,6 +439,9 @@ struct pe_ctx {
   pe::LedgerPlan ld_plan;
   HostBuf<pe::LedgerRec> ld_hin;
   DevBuf<pe::LedgerRec> ld_in;
+  // can a node's pods move elsewhere (pe_drain_fit_domains, pe_engine_drain.cpp): the plan with its node ->
+  // candidate map (kept all -1 between calls, sized by the inventory); the buffers are the domain calls' dm_*.
+  pe::DrainPlan dr_plan;
   // greedy
   DevBuf<ReqRec> g_groups;
   DevBuf<uint64_t> g_cand, g_bound;
@@ -598,7 +602,8 @@ inline void need_ptr(const void* p, const char* name) {
 // kernels_ms=<time>" (pe_gang_fit_domains) or "A=<active domains> rounds=<rounds launched> kernels_ms=<time>"
 // (pe_place_first_fit_domains) or "A=<active domains> U=<units> judged=<judgements> kernels_ms=<time>"
 // (pe_gang_preempt_domains) or "T=<records of this shard> steps=<steps> plan_us=<host plan time> kernels_ms=<time>"
-// (pe_release_gangs, pe_assume_gangs) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
+// (pe_release_gangs, pe_assume_gangs) or "A=<active domains> U=<units> E=<evicted pods> kernels_ms=<time>"
+// (pe_drain_fit_domains) in pe_last_error.  The variable is read on EVERY call, unlike the greedy's knobs: the latency tools switch
 // it on and off inside one process.
 struct CapEvents {
   pe_ctx* ctx;

@@ -754,4 +754,29 @@ static_assert(sizeof(LedgerRec) == 40, "LedgerRec must be 40 B");
 // in [0, stride).
 hipError_t launch_ledger_scatter(hipStream_t s, int64_t* res, int64_t stride, const LedgerRec* recs, int64_t n);
 
+// ---- can a node's pods move elsewhere, and where (pe_drain_fit_domains, pe_drain.hip; the plan: pe_drain_plan.h;
+// units and FitLarge records as for the fit call).  The member lists are launch_place_members', read-only here.
+// One candidate in plan order: its index in the caller's list, its node's GLOBAL id and its runs [g0, g1) --
+// PlaceGroup records whose count is the run's pods and whose pod0 is the run's first place in the slot list.  A
+// candidate's runs are consecutive in the slot list: its slots are the places [pod0 of g0, pod0 + count of g1 - 1).
+struct DrainPair {
+  int32_t cand, node, g0, g1;
+};
+static_assert(sizeof(DrainPair) == 16, "DrainPair must be 16 B");
+// The answers of a call, on the device, by the caller's candidate index: fits, moved and fail_slot; and target[S]
+// by pod slot (the caller sets every cell to -1; only the STORE instances touch it, and may be NULL for the others).
+struct DrainOut {
+  uint8_t* fits;
+  int64_t* moved;
+  int64_t* fail_slot;
+  int32_t* target;
+};
+// As launch_fit_units / launch_fit_large, with the candidate's node taken out of the working copy.  slot_list: the
+// evicted pod slots, every candidate's back to back.  store: write out.target.
+hipError_t launch_drain_units(hipStream_t s, const PlaceGroup* runs, const DrainPair* pairs, const FitUnit* units,
+                              int64_t U, const int32_t* slot_list, const PlaceSegs& segs, const DrainOut& out, bool store);
+hipError_t launch_drain_large(hipStream_t s, const PlaceGroup* runs, const DrainPair* pairs, const FitUnit* units,
+                              const FitLarge* large, int64_t n_large, int64_t* scratch, const int32_t* slot_list,
+                              const PlaceSegs& segs, const DrainOut& out, bool store);
+
 }  // namespace pe

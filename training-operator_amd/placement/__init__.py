@@ -24,7 +24,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY"]
 
@@ -190,6 +190,27 @@ class GangFit(NamedTuple):
     fail_group: Optional[np.ndarray]     # int32 [P]: -1, or the first group (within the job) not placed in full
     pods: Optional[np.ndarray]           # int64 [P]: pods the rule had placed when it stopped
     first: Optional[np.ndarray]          # int32 [J]: the smallest fitting pair of job j, -1 = none
+
+
+class DrainFit(NamedTuple):
+    """Engine.drain_fit_domains' answer; a part that was not asked for is None."""
+    fits: Optional[np.ndarray]           # uint8 [C]: 1 = the node's pods all find a node in the target domain right now
+    moved: Optional[np.ndarray]          # int64 [C]: pods that had found a node when the rule stopped
+    fail_slot: Optional[np.ndarray]      # int64 [C]: -1, or the pod slot of the first pod that found no node
+    target: Optional[np.ndarray]         # int32 [S]: the node the pod of slot s moves to, -1 = it does not move
+
+    def move_of(self, pod_node, node):
+        """(release_pod_node, assume_pod_node) int32 [S] for carrying out the move of candidate node `node`: with the
+        book's own gang_group_off, group_count and group_req, release_gangs(..., release_pod_node) gives back what the
+        node's pods hold and assume_gangs(..., assume_pod_node) takes it at their targets; every other slot is -1."""
+        if self.target is None:
+            raise ValueError("the call was made without targets")
+        pod = np.asarray(pod_node, dtype=np.int32).reshape(-1)
+        if pod.shape != self.target.shape:
+            raise ValueError("pod_node must be the call's [S]")
+        mine = pod == int(node)
+        none = np.int32(-1)
+        return np.where(mine, pod, none).astype(np.int32), np.where(mine, self.target, none).astype(np.int32)
 
 
 class GangPreempt(NamedTuple):
@@ -998,6 +1019,42 @@ class Engine:
         node's residuals.  Refused (PE_EINVAL, nothing changed) when a residual would fall below 0; only these totals
         are checked, not labels, needs or the best-fit rule.  Returns the number of pod slots that counted."""
         return self._ledger(self.lib.pe_assume_gangs, "pe_assume_gangs", gang_group_off, group_count, group_req, pod_node)
+
+    def drain_fit_domains(self, gang_group_off, group_count, group_req, group_need, pod_node, cand_node, cand_domain,
+                          level, level_size, parent=None, fits=True, moved=True, fail_slot=True, target=True) -> DrainFit:
+        """pe_drain_fit_domains: for every candidate c, would the pods that the book of placed gangs has on node
+        cand_node[c] all find a node in the level-`level` domain cand_domain[c], the node itself taken out, and
+        where?  Read-only.  The book is release_gangs' (gang_group_off [V + 1], group_count, group_req, pod_node = the
+        global node id of every pod slot, -1 = skipped) plus group_need; slots on nodes that are no candidate are
+        ignored.  level_size / parent describe the hierarchy exactly as for gang_capacity_tree.  Each of the four
+        answers can be left out (it then never crosses).  DrainFit.move_of gives the arrays that carry a move out."""
+        off = _c(gang_group_off, np.int32).reshape(-1)
+        cnt = _c(group_count, np.int32).reshape(-1)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32).reshape(-1)
+        pod = None if pod_node is None else _c(pod_node, np.int32).reshape(-1)
+        cn = _c(cand_node, np.int32).reshape(-1)
+        cd = _c(cand_domain, np.int32).reshape(-1)
+        if len(off) < 1 or len(cnt) != len(req) or (nd is not None and len(nd) != len(cnt)):
+            raise ValueError("gang_group_off must be [V + 1], group_count, group_req and group_need one row per group")
+        if cn.shape != cd.shape:
+            raise ValueError("cand_node and cand_domain must have one length")
+        S = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        if pod is not None and len(pod) < S:
+            raise ValueError("pod_node must hold one slot per pod")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        C = len(cn)
+        o_fits = np.zeros(C, dtype=np.uint8) if fits else None
+        o_moved = np.zeros(C, dtype=np.int64) if moved else None
+        o_fail = np.full(C, -1, dtype=np.int64) if fail_slot else None
+        o_target = np.full(S, -1, dtype=np.int32) if target else None
+        self._chk(self.lib.pe_drain_fit_domains(self.h, len(off) - 1, _p(off), _p(cnt), _p(req), _p(nd), _p(pod), C, _p(cn),
+                                                _p(cd), int(level), len(ls), _p(ls), _p(par), _p(o_fits), _p(o_moved),
+                                                _p(o_fail), _p(o_target)), "pe_drain_fit_domains")
+        return DrainFit(o_fits, o_moved, o_fail, o_target)
 
     def place_first_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
                                 pair_domain, level, level_size, parent=None, pairs=True):

@@ -108,6 +108,7 @@ SIGNATURES = {
                                                P, P, P, P]),
     "pe_release_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_assume_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
+    "pe_drain_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
