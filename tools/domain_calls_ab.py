@@ -5,7 +5,7 @@ from a checkout of it), in one job.
     python tools/domain_calls_ab.py OTHER_LIBRARY [tool ...]    the latency tools, each run other, tree, other
     python tools/domain_calls_ab.py --memory                    one context, every domain call once (PE_LIBRARY)
 
-The first form runs the named latency tools (default: the five domain calls') as child processes and prints, per
+The first form runs the named latency tools (default: the six domain calls') as child processes and prints, per
 row that reports a "call N us", the three medians, the spread of the other library's two runs and whether the
 tree stays within the slower of them plus that spread (the kernels' own time, where the row reports it, as a row
 of its own: it tells a move of the host side from one of the device side); then the second form under both
@@ -21,7 +21,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TOOLS = ["place_domains_latency.py", "gang_fit_latency.py", "first_fit_latency.py", "gang_preempt_latency.py",
-         "place_min_member_latency.py"]
+         "place_min_member_latency.py", "drain_fit_latency.py"]
 LIMIT = int(os.environ.get("AB_TOOL_LIMIT_S", "400"))
 
 

@@ -113,18 +113,20 @@ bool queue_segment_bounds(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A) {
   return true;
 }
 
-void large_segments_begin(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A) {
-  if (!queue_segment_bounds(ctx, segs, A)) return;
-  if (!ctx->dm_ev) hipchk(hipEventCreateWithFlags(&ctx->dm_ev, hipEventDisableTiming), "event create");
-  hipchk(hipEventRecord(ctx->dm_ev, ctx->stream), "event record");
-}
-
-LargeSegs large_segments(pe_ctx* ctx, const pe::FitPlan& plan) {
-  if (ctx->Ns <= pe::PL_LDS_NODES) return {};
+void launch_units_then_large(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A, const pe::FitPlan& plan,
+                             const std::function<void()>& launch_units,
+                             const std::function<void(const LargeSegs&)>& launch_large) {
+  const bool bounds = queue_segment_bounds(ctx, segs, A);
+  if (bounds) {
+    if (!ctx->dm_ev) hipchk(hipEventCreateWithFlags(&ctx->dm_ev, hipEventDisableTiming), "event create");
+    hipchk(hipEventRecord(ctx->dm_ev, ctx->stream), "event record");
+  }
+  launch_units();
+  if (!bounds) return;
   hipchk(hipEventSynchronize(ctx->dm_ev), "wait for the segment bounds");
   std::vector<pe::FitLarge> large;
   const int64_t nodes = pe::fit_scratch_layout(plan, ctx->dm_hoff.p, ctx->Ns, pe::PL_LDS_NODES, large);
-  if (large.empty()) return {};
+  if (large.empty()) return;
   const size_t bytes = large.size() * sizeof(pe::FitLarge);
   hipchk(ctx->dm_hlarge.ensure(bytes), "alloc pinned large-segment records");
   hipchk(ctx->dm_large.ensure(bytes), "alloc large-segment records");
@@ -136,7 +138,7 @@ LargeSegs large_segments(pe_ctx* ctx, const pe::FitPlan& plan) {
   std::memcpy(ctx->dm_hlarge.p, large.data(), bytes);
   hipchk(hipMemcpyAsync(ctx->dm_large.p, ctx->dm_hlarge.p, bytes, hipMemcpyHostToDevice, ctx->stream),
          "H2D large-segment records");
-  return {(const pe::FitLarge*)ctx->dm_large.p, (int64_t)large.size(), ctx->dm_scratch.p};
+  launch_large({(const pe::FitLarge*)ctx->dm_large.p, (int64_t)large.size(), ctx->dm_scratch.p});
 }
 
 void mirror_follow(pe_ctx* ctx, const char* kernel, int64_t J, const int32_t* job_group_off, const int64_t* group_req,

@@ -31,16 +31,19 @@ void launch_domain_members(pe_ctx* ctx, const int32_t* d_words, int64_t n_leaf, 
 // The segment bounds seg_off[A + 1] on their way to dm_hoff (queued; the caller synchronises), for a shard of more
 // than PL_LDS_NODES nodes: a smaller one has no segment above that.  Returns whether the copy was queued.
 bool queue_segment_bounds(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A);
-// The segments above PL_LDS_NODES nodes, in three steps: large_segments_begin queues the bounds' read-back with an
-// event behind it; the caller queues its LDS units; large_segments waits for the event, lays out the working copies
-// (fit_scratch_layout) and fills the records.  n == 0: no large segment (none can be in a shard that small).
+// The two launches of a judging call (fit, preempt, drain).  A segment above PL_LDS_NODES nodes needs the shard to
+// have that many: only then the bounds' read-back is queued, with an event behind it; launch_units queues the LDS
+// instance over the plan's units, so that the smaller segments' units already run; then the event is waited for,
+// the working copies are laid out (fit_scratch_layout), the records filled, and launch_large queues the other
+// instance over them -- where there is a large segment at all.
 struct LargeSegs {
   const pe::FitLarge* recs = nullptr;
   int64_t n = 0;
   int64_t* scratch = nullptr;
 };
-void large_segments_begin(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A);
-LargeSegs large_segments(pe_ctx* ctx, const pe::FitPlan& plan);
+void launch_units_then_large(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A, const pe::FitPlan& plan,
+                             const std::function<void()>& launch_units,
+                             const std::function<void(const LargeSegs&)>& launch_large);
 
 // The mirror and the stats follow a placing call's answer: for every placed job the request comes off the node of
 // each run of equal pod slots of its groups.  pod_off [G + 1]: the groups' slots; group_pods [G] (optional): only

@@ -118,14 +118,14 @@ int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group
     CapEvents ev(ctx);
     ev.begin();
     launch_domain_members(ctx, d_words, L0, A, segs);
-    large_segments_begin(ctx, segs, A);
-    hipchk(pe::launch_drain_units(ctx->stream, d_runs, d_pairs, d_units, U, d_slots, segs, out, store),
-           "launch drain_domains (LDS)");
-    const LargeSegs large = large_segments(ctx, plan.fit);
-    if (large.n > 0)
-      hipchk(pe::launch_drain_large(ctx->stream, d_runs, d_pairs, d_units, large.recs, large.n, large.scratch, d_slots,
-                                    segs, out, store),
-             "launch drain_domains (global)");
+    const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
+      hipchk(pe::launch_drain(ctx->stream, d_runs, d_pairs, d_units, blocks, large.recs, large.scratch, d_slots, segs, out,
+                              store),
+             what);
+    };
+    launch_units_then_large(
+        ctx, segs, A, plan.fit, [&]() { launch(U, {}, "launch drain_domains (LDS)"); },
+        [&](const LargeSegs& large) { launch(large.n, large, "launch drain_domains (global)"); });
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for
     const size_t lo = out_fits ? 0 : out_moved ? moved_at : out_fail_slot ? fail_at : target_at;

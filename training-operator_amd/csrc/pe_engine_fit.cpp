@@ -63,14 +63,12 @@ int pe_gang_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_of
     CapEvents ev(ctx);
     ev.begin();
     launch_domain_members(ctx, d_words, L0, A, segs);
-    // a segment above PL_LDS_NODES nodes needs the shard to have that many: only then the bounds come back, while
-    // the units of the smaller segments already run
-    large_segments_begin(ctx, segs, A);
-    hipchk(pe::launch_fit_units(ctx->stream, d_groups, d_pairs, d_units, U, segs, out), "launch fit_domains (LDS)");
-    const LargeSegs large = large_segments(ctx, plan);
-    if (large.n > 0)
-      hipchk(pe::launch_fit_large(ctx->stream, d_groups, d_pairs, d_units, large.recs, large.n, large.scratch, segs, out),
-             "launch fit_domains (global)");
+    const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
+      hipchk(pe::launch_fit(ctx->stream, d_groups, d_pairs, d_units, blocks, large.recs, large.scratch, segs, out), what);
+    };
+    launch_units_then_large(
+        ctx, segs, A, plan, [&]() { launch(U, {}, "launch fit_domains (LDS)"); },
+        [&](const LargeSegs& large) { launch(large.n, large, "launch fit_domains (global)"); });
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for
     const bool tables = out_fits || out_fail_group || out_pods;

@@ -133,14 +133,12 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
     launch_domain_members(ctx, d_words, L0, A, segs);
     hipchk(pe::launch_preempt_place_map(ctx->stream, segs, (int)A, ctx->Ns, (uint64_t)ctx->begin, ctx->pp_place.p),
            "launch preempt_place_map");
-    // a segment above PL_LDS_NODES nodes needs the shard to have that many: only then the bounds come back, while
-    // the units of the smaller segments already run
-    large_segments_begin(ctx, segs, A);
-    hipchk(pe::launch_preempt_units(ctx->stream, in, U, segs, out), "launch preempt_domains (LDS)");
-    const LargeSegs large = large_segments(ctx, fit);
-    if (large.n > 0)
-      hipchk(pe::launch_preempt_large(ctx->stream, in, large.recs, large.n, large.scratch, segs, out),
-             "launch preempt_domains (global)");
+    const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
+      hipchk(pe::launch_preempt(ctx->stream, in, blocks, large.recs, large.scratch, segs, out), what);
+    };
+    launch_units_then_large(
+        ctx, segs, A, fit, [&]() { launch(U, {}, "launch preempt_domains (LDS)"); },
+        [&](const LargeSegs& large) { launch(large.n, large, "launch preempt_domains (global)"); });
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for (the judgement counter
     // lies behind best and crosses with it, or alone for the diagnostics)

@@ -689,15 +689,12 @@ struct FitOut {
   int32_t* fail_group;
   int64_t* pods;
 };
-// One workgroup per unit u < U; those whose segment has at most PL_LDS_NODES nodes judge their pairs on a working
-// copy in LDS, the others leave at once.  PlaceGroup.pod0 is not read.
-hipError_t launch_fit_units(hipStream_t s, const PlaceGroup* groups, const FitPair* pairs, const FitUnit* units, int64_t U,
-                            const PlaceSegs& segs, const FitOut& out);
-// One workgroup per record of large[0 .. n_large): the units of a larger segment that the record names, on the
-// working copy scratch[at + d * n] (n = the segment's nodes).
-hipError_t launch_fit_large(hipStream_t s, const PlaceGroup* groups, const FitPair* pairs, const FitUnit* units,
-                            const FitLarge* large, int64_t n_large, int64_t* scratch, const PlaceSegs& segs,
-                            const FitOut& out);
+// large == NULL: one workgroup per unit u < blocks; those whose segment has at most PL_LDS_NODES nodes judge their
+// pairs on a working copy in LDS, the others leave at once.  Otherwise one workgroup per record of
+// large[0 .. blocks): the units of a larger segment that the record names, on the working copy
+// scratch[at + d * n] (n = the segment's nodes).  PlaceGroup.pod0 is not read.
+hipError_t launch_fit(hipStream_t s, const PlaceGroup* groups, const FitPair* pairs, const FitUnit* units, int64_t blocks,
+                      const FitLarge* large, int64_t* scratch, const PlaceSegs& segs, const FitOut& out);
 
 // ---- which gangs must go for a gang to fit (pe_gang_preempt_domains, pe_preempt.hip; the plan and its PreRec
 // records: pe_preempt_plan.h; units and FitLarge records as for the fit call).  The member lists are
@@ -735,10 +732,9 @@ struct PreOut {
 // node_place[n] = s for every place s of the segments (the caller preset every cell to -1).
 hipError_t launch_preempt_place_map(hipStream_t s, const PlaceSegs& segs, int A, int64_t Ns, uint64_t id_base,
                                     int32_t* node_place);
-// As launch_fit_units / launch_fit_large, for the two-phase walk of every pair.
-hipError_t launch_preempt_units(hipStream_t s, const PreIn& in, int64_t U, const PlaceSegs& segs, const PreOut& out);
-hipError_t launch_preempt_large(hipStream_t s, const PreIn& in, const FitLarge* large, int64_t n_large, int64_t* scratch,
-                                const PlaceSegs& segs, const PreOut& out);
+// As launch_fit, for the two-phase walk of every pair.
+hipError_t launch_preempt(hipStream_t s, const PreIn& in, int64_t blocks, const FitLarge* large, int64_t* scratch,
+                          const PlaceSegs& segs, const PreOut& out);
 
 // ---- giving back and re-taking placed gangs (pe_release_gangs, pe_assume_gangs, pe_ledger.hip)
 constexpr int LG_THREADS = 256;       // threads per block
@@ -771,12 +767,10 @@ struct DrainOut {
   int64_t* fail_slot;
   int32_t* target;
 };
-// As launch_fit_units / launch_fit_large, with the candidate's node taken out of the working copy.  slot_list: the
-// evicted pod slots, every candidate's back to back.  store: write out.target.
-hipError_t launch_drain_units(hipStream_t s, const PlaceGroup* runs, const DrainPair* pairs, const FitUnit* units,
-                              int64_t U, const int32_t* slot_list, const PlaceSegs& segs, const DrainOut& out, bool store);
-hipError_t launch_drain_large(hipStream_t s, const PlaceGroup* runs, const DrainPair* pairs, const FitUnit* units,
-                              const FitLarge* large, int64_t n_large, int64_t* scratch, const int32_t* slot_list,
-                              const PlaceSegs& segs, const DrainOut& out, bool store);
+// As launch_fit, with the candidate's node taken out of the working copy.  slot_list: the evicted pod slots, every
+// candidate's back to back.  store: write out.target.
+hipError_t launch_drain(hipStream_t s, const PlaceGroup* runs, const DrainPair* pairs, const FitUnit* units, int64_t blocks,
+                        const FitLarge* large, int64_t* scratch, const int32_t* slot_list, const PlaceSegs& segs,
+                        const DrainOut& out, bool store);
 
 }  // namespace pe

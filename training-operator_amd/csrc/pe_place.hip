@@ -11,8 +11,11 @@
 // bits), so no result depends on that order.  A domain without nodes has a zero-length segment and still
 // gets its workgroup, which fails the jobs that have pods and passes the others.
 //
-// place_domains_kernel: the workgroup walks its jobs in plan order, group by group.  The decision itself is
-// pe_place_step.h's, shared with the read-only what-if of pe_fit.hip.  Per decision every
+// place_domains_kernel: the workgroup walks its jobs in plan order, group by group.  The decision and the walk
+// of a job's groups through it are pe_place_step.h's, shared with every other domain call; the log, the pod
+// stores, the rollback (place_job) and the stage / run / write-back frame of the kernel (place_frame) are
+// pe_place_job.h's, shared with pe_place_min.hip; this file owns the member lists, a domain's loop over its
+// jobs and the first-fit rounds.  Per decision every
 // thread scores its share of the segment with node_key (pe_node_key.h) against the working residuals and
 // finds what its own best node would take; a wave butterfly (pe_wave.h) and one cross-wave step through LDS
 // give the block's minimum key with that node's place and take.  The chosen node takes
@@ -137,55 +140,20 @@ __device__ __forceinline__ void place_domain(int64_t* r0, const uint32_t* gid, S
   }
 }
 
-// IN_LDS: the instance for the segments of at most PL_LDS_NODES nodes, whose working state it stages in LDS;
-// the other instance takes the larger segments and works on the global segment in place.  Both are launched
-// over all the active domains and a workgroup whose segment is the other instance's leaves at once (one
-// kernel with both paths held more uniform values than there are SGPRs).
+// place_frame (pe_place_job.h) around place_domain.  IN_LDS: the instance for the segments of at most
+// PL_LDS_NODES nodes, whose working state it stages in LDS; the other instance takes the larger segments and
+// works on the global segment in place.  Both are launched over all the active domains and a workgroup whose
+// segment is the other instance's leaves at once (one kernel with both paths held more uniform values than
+// there are SGPRs).
 template <bool IN_LDS>
 __global__ __launch_bounds__(PL_THREADS) void place_domains_kernel(
     const PlaceGroup* __restrict__ groups, const PlaceJob* __restrict__ jobs, const int32_t* __restrict__ job_start,
     PlaceSegs sg, int64_t* __restrict__ res, int64_t stride, uint32_t id_base, int32_t* __restrict__ out_pod,
     int32_t* __restrict__ out_status, int32_t* __restrict__ log) {
-  __shared__ PlaceMin mn;
-  const int a = blockIdx.x, tid = threadIdx.x;
-  const int b = sg.seg_off[a], n = sg.seg_off[a + 1] - b;
-  if ((n <= PL_LDS_NODES) != IN_LDS) return;
-  const int j0 = job_start[a], j1 = job_start[a + 1];
-  int64_t* const g0 = sg.res + b;
-  const int64_t ss = sg.seg_stride;
-  int64_t* const g1 = g0 + ss;
-  int64_t* const g2 = g1 + ss;
-  int64_t* const g3 = g2 + ss;
-  const uint32_t* const gid = sg.gid + b;
-  if constexpr (IN_LDS) {
-    __shared__ PlaceShared sh;
-    for (int i = tid; i < n; i += PL_THREADS) {   // thread i mod PL_THREADS owns place i: no barrier
-      sh.r[0][i] = g0[i];
-      sh.r[1][i] = g1[i];
-      sh.r[2][i] = g2[i];
-      sh.r[3][i] = g3[i];
-      sh.lab[i] = gid[ss + i];
-      sh.gid[i] = gid[i];
-    }
-    place_domain(sh.r[0], sh.gid, std::integral_constant<int, PL_LDS_NODES>(), n, mn, groups, jobs, j0, j1, out_pod,
-                 out_status, log);
-    for (int i = tid; i < n; i += PL_THREADS) {
-      const int64_t l = (int64_t)(sh.gid[i] - id_base);   // < Ns: the fill kernel wrote id_base + local
-      res[l] = sh.r[0][i];
-      res[stride + l] = sh.r[1][i];
-      res[2 * stride + l] = sh.r[2][i];
-      res[3 * stride + l] = sh.r[3][i];
-    }
-  } else {
-    place_domain(g0, gid, ss, n, mn, groups, jobs, j0, j1, out_pod, out_status, log);
-    for (int i = tid; i < n; i += PL_THREADS) {
-      const int64_t l = (int64_t)(gid[i] - id_base);
-      res[l] = g0[i];
-      res[stride + l] = g1[i];
-      res[2 * stride + l] = g2[i];
-      res[3 * stride + l] = g3[i];
-    }
-  }
+  place_frame<IN_LDS>(sg, res, stride, id_base, [&](int64_t* r0, const uint32_t* gid, auto rs, int n, PlaceMin& mn) {
+    const int a = blockIdx.x;
+    place_domain(r0, gid, rs, n, mn, groups, jobs, job_start[a], job_start[a + 1], out_pod, out_status, log);
+  });
 }
 
 // ---- pe_place_first_fit_domains: one round.  The workgroup of active domain a looks at the head of its queue.

@@ -9,19 +9,18 @@
 // through a shifted out_pod to the slots among all slots.  A job that fails phase 1 gets -1 in ALL its slots and
 // leaves its groups' counts at the 0 the caller filled them with; phase 2 is not tried.
 //
-// Phase 2 walks the job's OPTIONAL records in order with the same decision (place_decide, place_take of
-// pe_place_step.h): t = min(pods left, floor(res / q)) pods per decision, so a count of 2^31 - 1 with a zero
-// request is one decision; an optional island group is one decision for count x request or nothing.  The first
+// Phase 2 (place_optional, this file's) walks the job's OPTIONAL records in order, each through the one-group
+// walk of pe_place_step.h (place_group): t = min(pods left, floor(res / q)) pods per decision, so a count of
+// 2^31 - 1 with a zero request is one decision; an optional island group is one decision for count x request or
+// nothing.  The first
 // decision of a group that finds no node ends that group: its remaining slots become -1 and the walk goes on with
 // the next group.  Nothing of phase 2 is logged or rolled back.  Between decisions the working state is read and
 // written by its owner thread only (thread i mod PL_THREADS owns place i), as in phase 1, so phase 2 adds no
 // barrier of its own; after a rollback place_job has already synchronised.
 //
 // The working state lives in LDS for segments up to PL_LDS_NODES nodes and in the global segment beyond: two
-// instances, as place_domains_kernel.
+// instances, as place_domains_kernel, on the same frame (place_frame, pe_place_job.h).
 #include <hip/hip_runtime.h>
-
-#include <type_traits>
 
 #include "pe_kernels.h"
 #include "pe_place_job.h"
@@ -39,35 +38,21 @@ __device__ __forceinline__ void place_optional(int64_t* r0, const uint32_t* gid,
                                                int g0, int g1, int32_t* __restrict__ out_pod,
                                                int32_t* __restrict__ out_group_pods) {
   const int tid = threadIdx.x;
-  int64_t* const r1 = r0 + rs;
-  int64_t* const r2 = r1 + rs;
-  int64_t* const r3 = r2 + rs;
-  const uint32_t* const lab = gid + rs;
   for (int g = g0; g < g1; ++g) {
     const PlaceMinOpt op = opt[g];
-    const int32_t mand = groups[g].count;
-    uint32_t left = op.count > 0 ? (uint32_t)op.count : 0u;
-    if (left > 0) {
-      PlaceGroup gr = groups[g];
-      gr.count = op.count;   // an optional island group is optional as a whole: its unit is op.count x request
-      const bool unit = (gr.need & NEED_ISLAND) != 0;   // its one unit or nothing
-      int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];
-      const bool fits = !unit || island_request(gr, s0, s1, s2, s3);   // a product that overflows fits nowhere
-      int64_t slot = op.pod0;
-      while (fits && left > 0) {
-        const PlaceChoice c = place_decide(r0, r1, r2, r3, gid, lab, n, s0, s1, s2, s3, gr.need, unit, left, mn, par);
-        if (c.none()) break;   // no node of the domain fits: the group's remaining pods stay pending
-        place_take(r0, r1, r2, r3, c, unit, s0, s1, s2, s3);
-        const uint32_t t = c.t;
-        const int32_t node = (int32_t)(c.klo & 0xFFFFFFu);
-        for (int64_t p = slot + tid; p < slot + t; p += PL_THREADS) out_pod[p] = node;   // slot + t <= the group's end
-        slot += t;
-        left -= t;
-      }
-      for (int64_t p = slot + tid; p < slot + left; p += PL_THREADS) out_pod[p] = -1;
-    }
+    PlaceGroup gr = groups[g];
+    const int32_t mand = gr.count;
+    gr.count = op.count;   // an optional island group is optional as a whole: its unit is op.count x request
+    // a group that finds no node ends there, and the walk goes on with the next: its pods left stay pending
+    const uint32_t left = place_group(r0, rs, gid, gid + rs, n, mn, par, gr, [&](const PlaceChoice& c, uint32_t done) {
+      const int32_t node = (int32_t)(c.klo & 0xFFFFFFu);
+      const int64_t slot = op.pod0 + done;   // slot + t <= the group's end
+      for (int64_t p = slot + tid; p < slot + c.t; p += PL_THREADS) out_pod[p] = node;
+    });
+    const int32_t placed = op.count > 0 ? op.count - (int32_t)left : 0;
+    for (int64_t p = op.pod0 + placed + tid; p < op.pod0 + placed + left; p += PL_THREADS) out_pod[p] = -1;
     // mandatory + optional placed <= the group's count <= 2^31 - 1
-    if (tid == 0) out_group_pods[g] = mand + (op.count > 0 ? op.count - (int32_t)left : 0);
+    if (tid == 0) out_group_pods[g] = mand + placed;
   }
 }
 
@@ -97,55 +82,18 @@ __device__ __forceinline__ void place_min_domain(int64_t* r0, const uint32_t* gi
   }
 }
 
-// IN_LDS as for place_domains_kernel: the instance for the segments of at most PL_LDS_NODES nodes stages the
-// working state in LDS, the other works on the global segment in place; a workgroup whose segment is the other
-// instance's leaves at once.
+// place_frame around place_min_domain, IN_LDS as for place_domains_kernel.
 template <bool IN_LDS>
 __global__ __launch_bounds__(PL_THREADS) void place_min_domains_kernel(
     const PlaceGroup* __restrict__ groups, const PlaceMinOpt* __restrict__ opt, const PlaceMinJob* __restrict__ jobs,
     const int32_t* __restrict__ job_start, PlaceSegs sg, int64_t* __restrict__ res, int64_t stride, uint32_t id_base,
     int32_t* __restrict__ out_pod, int32_t* __restrict__ out_status, int32_t* __restrict__ out_group_pods,
     int32_t* __restrict__ log) {
-  __shared__ PlaceMin mn;
-  const int a = blockIdx.x, tid = threadIdx.x;
-  const int b = sg.seg_off[a], n = sg.seg_off[a + 1] - b;
-  if ((n <= PL_LDS_NODES) != IN_LDS) return;
-  const int j0 = job_start[a], j1 = job_start[a + 1];
-  int64_t* const g0 = sg.res + b;
-  const int64_t ss = sg.seg_stride;
-  int64_t* const g1 = g0 + ss;
-  int64_t* const g2 = g1 + ss;
-  int64_t* const g3 = g2 + ss;
-  const uint32_t* const gid = sg.gid + b;
-  if constexpr (IN_LDS) {
-    __shared__ PlaceShared sh;
-    for (int i = tid; i < n; i += PL_THREADS) {   // thread i mod PL_THREADS owns place i: no barrier
-      sh.r[0][i] = g0[i];
-      sh.r[1][i] = g1[i];
-      sh.r[2][i] = g2[i];
-      sh.r[3][i] = g3[i];
-      sh.lab[i] = gid[ss + i];
-      sh.gid[i] = gid[i];
-    }
-    place_min_domain(sh.r[0], sh.gid, std::integral_constant<int, PL_LDS_NODES>(), n, mn, groups, opt, jobs, j0, j1,
-                     out_pod, out_status, out_group_pods, log);
-    for (int i = tid; i < n; i += PL_THREADS) {
-      const int64_t l = (int64_t)(sh.gid[i] - id_base);   // < Ns: the fill kernel wrote id_base + local
-      res[l] = sh.r[0][i];
-      res[stride + l] = sh.r[1][i];
-      res[2 * stride + l] = sh.r[2][i];
-      res[3 * stride + l] = sh.r[3][i];
-    }
-  } else {
-    place_min_domain(g0, gid, ss, n, mn, groups, opt, jobs, j0, j1, out_pod, out_status, out_group_pods, log);
-    for (int i = tid; i < n; i += PL_THREADS) {
-      const int64_t l = (int64_t)(gid[i] - id_base);
-      res[l] = g0[i];
-      res[stride + l] = g1[i];
-      res[2 * stride + l] = g2[i];
-      res[3 * stride + l] = g3[i];
-    }
-  }
+  place_frame<IN_LDS>(sg, res, stride, id_base, [&](int64_t* r0, const uint32_t* gid, auto rs, int n, PlaceMin& mn) {
+    const int a = blockIdx.x;
+    place_min_domain(r0, gid, rs, n, mn, groups, opt, jobs, job_start[a], job_start[a + 1], out_pod, out_status,
+                     out_group_pods, log);
+  });
 }
 
 }  // namespace

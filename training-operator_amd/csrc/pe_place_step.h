@@ -1,9 +1,13 @@
-// One decision of the Appendix-B rule inside a domain's segment, shared by the domain placement (pe_place.hip)
-// and its read-only what-if (pe_fit.hip): one statement of the decision for both kernels (device code only).
-// Every thread scores its share of the segment with node_key (pe_node_key.h) against the working residuals
-// and finds what its own best node would take; a wave butterfly (pe_wave.h) and one cross-wave step through LDS
-// give the block's minimum key with that node's place and take.  Thread i mod PL_THREADS is the only one that
-// reads or writes place i of the working state, so a decision costs one barrier.
+// The Appendix-B rule inside a domain's segment, stated once for every domain call (device code only): one
+// DECISION (place_decide, place_take) and the WALK of a job's groups through it (place_group, place_groups), the
+// only place where the island test, island_request, the loop over the pods left, none() and place_take are strung
+// together.  The placing kernels (pe_place_job.h: place_job; pe_place_min.hip: place_optional) and the what-if
+// kernels (pe_fit.hip, pe_preempt.hip, pe_drain.hip, framed by pe_what_if.h) are callers that say what happens
+// after a take.
+// Per decision every thread scores its share of the segment with node_key (pe_node_key.h) against the working
+// residuals and finds what its own best node would take; a wave butterfly (pe_wave.h) and one cross-wave step
+// through LDS give the block's minimum key with that node's place and take.  Thread i mod PL_THREADS is the only
+// one that reads or writes place i of the working state, so a decision costs one barrier.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -109,6 +113,48 @@ __device__ __forceinline__ void place_take(int64_t* r0, int64_t* r1, int64_t* r2
   r1[c.at] -= m * s1;
   r2[c.at] -= m * s2;
   r3[c.at] -= m * s3;
+}
+
+// One group on the working state w0[d * ws + i] (written) of n places with ids gid and labels lab, until its pods
+// are placed or one finds no node: the pods left (0: placed in full, or count <= 0), the same on every thread.  An
+// island group is one decision for count x request, and a product that overflows fits nowhere.
+// on_take(c, done) follows every take; done: the group's pods placed before it.  Called by the whole workgroup.
+template <class Stride, class OnTake>
+__device__ __forceinline__ uint32_t place_group(int64_t* w0, Stride ws, const uint32_t* gid, const uint32_t* lab, int n,
+                                                PlaceMin& mn, int& par, const PlaceGroup& gr, OnTake&& on_take) {
+  if (gr.count <= 0) return 0;
+  int64_t* const w1 = w0 + ws;
+  int64_t* const w2 = w1 + ws;
+  int64_t* const w3 = w2 + ws;
+  const bool unit = (gr.need & NEED_ISLAND) != 0;
+  int64_t s0 = gr.q[0], s1 = gr.q[1], s2 = gr.q[2], s3 = gr.q[3];   // the request the scan scores
+  uint32_t left = (uint32_t)gr.count;
+  if (unit && !island_request(gr, s0, s1, s2, s3)) return left;
+  while (left > 0) {
+    const PlaceChoice c = place_decide(w0, w1, w2, w3, gid, lab, n, s0, s1, s2, s3, gr.need, unit, left, mn, par);
+    if (c.none()) break;   // no node of the domain fits
+    place_take(w0, w1, w2, w3, c, unit, s0, s1, s2, s3);
+    on_take(c, (uint32_t)gr.count - left);
+    left -= c.t;
+  }
+  return left;
+}
+
+// Groups [g0, g1) in order, stopping at the first that is not placed in full: that group (g1: all placed) and, in
+// `left`, its pods left.  on_take(g, gr, c, done) as place_group's, with the group's index and record.
+template <class Stride, class OnTake>
+__device__ __forceinline__ int place_groups(int64_t* w0, Stride ws, const uint32_t* gid, const uint32_t* lab, int n,
+                                            PlaceMin& mn, int& par, const PlaceGroup* __restrict__ groups, int g0, int g1,
+                                            uint32_t& left, OnTake&& on_take) {
+  left = 0;
+  int g = g0;
+  while (g < g1 && left == 0) {
+    const PlaceGroup gr = groups[g];
+    left = place_group(w0, ws, gid, lab, n, mn, par, gr,
+                       [&](const PlaceChoice& c, uint32_t done) { on_take(g, gr, c, done); });
+    g += 1 - (int)min(left, 1u);   // past a group placed in full (g += left == 0 took the flag through a VGPR)
+  }
+  return g;
 }
 
 }  // namespace pe
