@@ -1106,6 +1106,47 @@ func (e *Engine) DrainFitDomains(v *Victims, groupNeed []uint32, candNode, candD
 	return fits, moved, failSlot, target, e.err(rc, "pe_drain_fit_domains")
 }
 
+// ScaleUp is ScaleUpDomains' answer: per pair the fewest new nodes (-1 = none up to the pair's maximum), the deciding
+// attempt's failing group (-1 = placed), its pods and those of them on new nodes; per job the pair with the fewest
+// new nodes, ties to the smallest pair, -1 = none.  With selectionOnly the per-pair slices are nil.
+type ScaleUp struct {
+	Nodes, FailGroup []int32
+	Pods, NewPods    []int64
+	Best             []int32
+}
+
+// ScaleUpDomains answers, for every pair p, how many nodes of template pairTemplate[p] -- free residual tmplRes[t]
+// ([T][4] flattened), labels tmplLabels[t] (nil = 0) -- would have to join the level-`level` domain pairDomain[p] for
+// PlaceGreedyDomains to place job pairJob[p] alone there (pe_scale_up_domains).  The i-th new node has id newSlot[i],
+// a removed slot of the inventory; attempts run with 0, 1, ... pairMax[p] new nodes (nil = len(newSlot)) in that
+// order, since the answer is not monotone.  Read-only.  selectionOnly leaves the four per-pair answers out (nothing
+// pair-sized crosses).  levelSize and parent describe the hierarchy exactly as for GangCapacityTree.  A sharded engine
+// refuses the call.
+func (e *Engine) ScaleUpDomains(g *Gangs, tmplRes []int64, tmplLabels []uint32, newSlot, pairJob, pairDomain, pairTemplate, pairMax []int32, level int32, levelSize, parent []int32, selectionOnly bool) (ScaleUp, error) {
+	J := len(g.JobGroupOff) - 1
+	P := len(pairJob)
+	T := len(tmplRes) / 4
+	if len(pairDomain) != P || len(pairTemplate) != P || (pairMax != nil && len(pairMax) != P) {
+		return ScaleUp{}, fmt.Errorf("ScaleUpDomains: %d jobs for %d domains, %d templates and %d maxima", P, len(pairDomain), len(pairTemplate), len(pairMax))
+	}
+	if len(tmplRes) != 4*T || (tmplLabels != nil && len(tmplLabels) != T) {
+		return ScaleUp{}, fmt.Errorf("ScaleUpDomains: %d residual cells and %d labels for %d templates", len(tmplRes), len(tmplLabels), T)
+	}
+	out := ScaleUp{Best: make([]int32, J)}
+	if !selectionOnly {
+		out.Nodes = make([]int32, P)
+		out.FailGroup = make([]int32, P)
+		out.Pods = make([]int64, P)
+		out.NewPods = make([]int64, P)
+	}
+	rc := C.pe_scale_up_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.GroupCount), ptr64(g.GroupReq),
+		ptru32(g.GroupNeed), C.int32_t(T), ptr64(tmplRes), ptru32(tmplLabels), C.int32_t(len(newSlot)), ptr32(newSlot),
+		C.int64_t(P), ptr32(pairJob), ptr32(pairDomain), ptr32(pairTemplate), ptr32(pairMax), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(out.Nodes), ptr32(out.FailGroup), ptr64(out.Pods),
+		ptr64(out.NewPods), ptr32(out.Best))
+	return out, e.err(rc, "pe_scale_up_domains")
+}
+
 // Synchronize waits for the context's stream; Stream is its hipStream_t (for event timing).
 func (e *Engine) Synchronize() error { return e.err(C.pe_synchronize(e.ctx), "pe_synchronize") }
 

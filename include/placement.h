@@ -968,6 +968,74 @@ int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group
                          uint8_t* out_fits /*[C] or NULL*/, int64_t* out_moved /*[C] or NULL*/,
                          int64_t* out_fail_slot /*[C] or NULL*/, int32_t* out_target /*[S] or NULL*/);
 
+/* (ABI 7, additive) Fewest new nodes for a gang to fit a domain: the question that follows pe_gang_fit_domains' "no"
+ * when nothing can be evicted.  How many nodes of THIS node type would have to join THIS rack for the gang to be
+ * placed there, and which (node type, rack) choice needs the fewest?  It is the cluster autoscaler's scale-up
+ * simulation (binpacking estimator, "least nodes" expander) and what Kueue's provisioning request asks before it
+ * admits a gang; without this call the only way to learn the answer is PE_NODE_SET of k template nodes, a
+ * pe_gang_fit_domains and PE_NODE_REMOVE, once per k.  NO reference function, as pe_gang_fit_domains.  Read-only.
+ * Jobs, groups, counts, requests, needs, pair_job, pair_domain, level, level_size, parent and dom_level(n) mean
+ * exactly what they mean in pe_gang_fit_domains, and so does the judgement: would pe_place_greedy_domains, given
+ * this single job in this domain and no other job, return PE_JOB_PLACED?
+ *   Templates   tmpl_res[t] is the free residual of a fresh node of type t (cap - used with the daemonsets
+ *               counted, every cell >= 0), tmpl_labels[t] its labels.
+ *   New slots   new_slot lists the free slots the caller's Node informer would hand to new nodes, in the order it
+ *               would hand them out: each in [0, n_total), a removed slot now, named once.  The i-th new node of
+ *               ANY pair has id new_slot[i]; ids matter because the Appendix-B key breaks score ties by node id.
+ *   Attempt k   of pair p, 0 <= k <= K_p = pair_max[p], is the judgement on a widened inventory: the nodes of
+ *               domain pair_domain[p] with their CURRENT residuals plus k further members of the domain, new node
+ *               i < k with residual tmpl_res[pair_template[p]], labels tmpl_labels[...] | PE_LABEL_ISLAND (a node
+ *               in a domain has an island; the caller's bit 31 is replaced) and id new_slot[i].  Every attempt
+ *               starts from fresh residuals, real and new.  Equivalently: what pe_gang_fit_domains answers for
+ *               (job, domain) after PE_NODE_SET put the template on new_slot[0 .. k) with used 0 and an island
+ *               that is a leaf under the domain.
+ * The answer is NOT monotone in k, so the attempts are tried in ascending order and the first that places the job
+ * is the answer -- no bisection, no try from the top:
+ *   out_nodes[p]      = the smallest k in [0, K_p] whose attempt places the job, -1 when there is none.  With
+ *                       K_p = 0 it is pe_gang_fit_domains' out_fits[p] - 1.
+ *   The DECIDING attempt is k = out_nodes[p], or attempt K_p when the answer is -1.
+ *   out_fail_group[p],
+ *   out_pods[p]       = pe_gang_fit_domains' two outputs for the deciding attempt: -1 and the job's pod total when
+ *                       the pair is answered, else what still does not fit with every allowed node present (a
+ *                       group larger than the template shows here)
+ *   out_new_pods[p]   = the pods of the deciding attempt that sit on new nodes (an island group: its count)
+ *   out_best[j]       = the pair of job j with the smallest out_nodes >= 0, ties to the smallest p, -1 when there
+ *                       is none.  With every K_p = 0 it equals pe_gang_fit_domains' out_first.
+ * out_best is computed on the device; a caller who wants only the selection passes the four P-sized outputs NULL
+ * and nothing P-sized crosses.  Each out_* may be NULL; group_need NULL = 0, tmpl_labels NULL = 0, pair_max NULL =
+ * n_new for every pair.
+ * A domain without nodes is a legitimate pair: with k >= 1 it holds what k template nodes hold.  Pairs are judged
+ * alone: two pairs may be promised the same new nodes, so act on one and ask again.  n_pairs == 0 and n_jobs == 0
+ * are PE_OK (with n_jobs > 0 and no pairs out_best is all -1).
+ * Worked example: a rack holds one node with 8 free GPUs, the template has 4 GPUs, the job is A = 1 x 4 GPUs
+ * followed by B = 1 x 8 GPUs.  k = 0: A takes the only node and B fails.  k = 1: A takes the new node, the
+ * tightest fit, and B takes the old one -- out_nodes 1, out_new_pods 1.
+ * A non-monotone case (cpu m, GPUs; memory and storage 0): a rack of two nodes with (15000, 8) and (14000, 7) free,
+ * the template (9000, 2), new ids above the real ones, and the job 2 x (6000, 1), 1 x (7000, 7), 1 x (2000, 1),
+ * 2 x (8000, 0).  It is placed with k = 1, 3 and 4 new nodes and NOT with k = 0 or 2: out_nodes 1.
+ * Acting on the answer: once the nodes have arrived (PE_NODE_SET), pe_place_greedy_domains gives the pods' nodes.
+ * Read-only: the device residuals, the host mirror, the reset snapshot, labels and islands, the staged fit batch
+ * and pe_stats are left exactly as they are, and nothing is kept between calls.
+ * Sharded contexts: with world_size > 1 the call is PE_EINVAL (a domain may span shards).
+ * PE_EINVAL, nothing written (the first offending index in pe_last_error where there is one), checked in this
+ * order: everything pe_gang_fit_domains refuses; n_templates < 0, or < 1 with pairs; a NULL tmpl_res with
+ * templates; a negative tmpl_res cell; n_new outside [0, PE_MAX_SCALE_NODES]; a NULL new_slot with n_new > 0; a
+ * new_slot that is out of range, not a removed slot, or repeated; a NULL pair_template with pairs; a pair_template
+ * outside [0, n_templates); a pair_max outside [0, n_new].  PE_ESTATE / PE_ENOMEM: as pe_gang_fit_domains. */
+#define PE_MAX_SCALE_NODES 64
+int pe_scale_up_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off /*[J+1]*/,
+                        const int32_t* group_count /*[G]*/, const int64_t* group_req /*[G][4]*/,
+                        const uint32_t* group_need /*[G] or NULL = 0*/,
+                        int32_t n_templates, const int64_t* tmpl_res /*[T][4]*/, const uint32_t* tmpl_labels /*[T] or NULL = 0*/,
+                        int32_t n_new, const int32_t* new_slot /*[n_new]*/,
+                        int64_t n_pairs, const int32_t* pair_job /*[P]*/, const int32_t* pair_domain /*[P]*/,
+                        const int32_t* pair_template /*[P]*/, const int32_t* pair_max /*[P] or NULL = n_new*/,
+                        int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                        const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                        int32_t* out_nodes /*[P] or NULL*/, int32_t* out_fail_group /*[P] or NULL*/,
+                        int64_t* out_pods /*[P] or NULL*/, int64_t* out_new_pods /*[P] or NULL*/,
+                        int32_t* out_best /*[J] or NULL*/);
+
 /* ---- Host resolver: the host half of pe_place_greedy, exposed on its own so a caller (or a
  * CPU test) can drive the windowed protocol with candidate blobs it obtained elsewhere, e.g. one
  * blob per shard gathered over any transport.  No device is touched.

@@ -31,8 +31,8 @@ void launch_domain_members(pe_ctx* ctx, const int32_t* d_words, int64_t n_leaf, 
 // The segment bounds seg_off[A + 1] on their way to dm_hoff (queued; the caller synchronises), for a shard of more
 // than PL_LDS_NODES nodes: a smaller one has no segment above that.  Returns whether the copy was queued.
 bool queue_segment_bounds(pe_ctx* ctx, const pe::PlaceSegs& segs, int64_t A);
-// The two launches of a judging call (fit, preempt, drain).  A segment above PL_LDS_NODES nodes needs the shard to
-// have that many: only then the bounds' read-back is queued, with an event behind it; launch_units queues the LDS
+// The two launches of a judging call (fit, preempt, drain, scale-up).  A segment above PL_LDS_NODES nodes needs the
+// shard to have that many: only then the bounds' read-back is queued, with an event behind it; launch_units queues the LDS
 // instance over the plan's units, so that the smaller segments' units already run; then the event is waited for,
 // the working copies are laid out (fit_scratch_layout), the records filled, and launch_large queues the other
 // instance over them -- where there is a large segment at all.

@@ -773,4 +773,41 @@ hipError_t launch_drain(hipStream_t s, const PlaceGroup* runs, const DrainPair* 
                         const FitLarge* large, int64_t* scratch, const int32_t* slot_list, const PlaceSegs& segs,
                         const DrainOut& out, bool store);
 
+// ---- fewest new nodes for a gang to fit a domain (pe_scale_up_domains, pe_scale.hip; the plan: pe_scale_plan.h;
+// units -- cut by weight -- and FitLarge records as for the fit call).  The member lists are launch_place_members',
+// read-only here.
+constexpr int SCALE_MAX_NODES = 64;   // PE_MAX_SCALE_NODES: a thread holds at most one new place
+static_assert(SCALE_MAX_NODES <= PL_THREADS, "one new place per thread");
+// One pair in plan order: its index in the caller's list, its job, the job's groups [g0, g1), its template and the
+// largest number of new nodes to try, in [0, n_new].
+struct ScalePair {
+  int32_t pair, job, g0, g1, tmpl, kmax, pad_[2];
+};
+static_assert(sizeof(ScalePair) == 32, "ScalePair must be 32 B");
+// What the judging kernels read besides the segments.  tmpl_res [T][4] and tmpl_lab [T]: a fresh node's residual
+// and its labels, the island bit already set; new_slot [n_new]: the GLOBAL ids of the new nodes, in the order
+// they are handed out.
+struct ScaleIn {
+  const PlaceGroup* groups;
+  const ScalePair* pairs;
+  const FitUnit* units;
+  const int64_t* tmpl_res;
+  const uint32_t* tmpl_lab;
+  const int32_t* new_slot;
+  int32_t n_new;
+};
+// The answers of a call, on the device: best[J] (the caller sets every cell to ~0; unsigned minimum of
+// nodes << 32 | pair over the pairs with an answer), and per pair, by the caller's pair index, nodes, fail_group,
+// pods and new_pods.
+struct ScaleOut {
+  unsigned long long* best;
+  int32_t* nodes;
+  int32_t* fail_group;
+  int64_t* pods;
+  int64_t* new_pods;
+};
+// As launch_fit, for the ascending attempts of every pair.  PlaceGroup.pod0 is not read.
+hipError_t launch_scale(hipStream_t s, const ScaleIn& in, int64_t blocks, const FitLarge* large, int64_t* scratch,
+                        const PlaceSegs& segs, const ScaleOut& out);
+
 }  // namespace pe

@@ -1,6 +1,6 @@
-// The frame of the read-only what-if kernels (pe_fit.hip, pe_preempt.hip, pe_drain.hip; device code only): each
-// judges the pairs of its units on a private working copy of their segment's four residual rows, which a fresh
-// copy per judgement discards.  what_if_units finds the workgroup's units and working state and hands them to the
+// The frame of the read-only what-if kernels (pe_fit.hip, pe_preempt.hip, pe_drain.hip, pe_scale.hip; device code
+// only): each judges the pairs of its units on a private working copy of their segment's four residual rows, which a
+// fresh copy per judgement discards.  what_if_units finds the workgroup's units and working state and hands them to the
 // kernel's body, what_if_copy is the fresh copy; the groups' walk is pe_place_step.h's.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _abi
-from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
+from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SCALE_NODES, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -24,7 +24,7 @@ V1, V2 = PE_MODE_V1, PE_MODE_V2
 __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "PE_JOB_PLACED", "PE_JOB_UNSCHEDULABLE",
            "PE_KIND_CONTAINER", "PE_KIND_INIT", "PE_KIND_SIDECAR", "PE_KIND_OVERHEAD", "PE_KIND_SHIFT", "comm_id",
            "PE_NODE_SET", "PE_NODE_REMOVE", "PE_CAP_MAX", "wide_ints", "wide_limbs", "PE_MAX_DOMAINS", "DomainCapacity",
-           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
+           "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "ScaleUp", "PE_MAX_SCALE_NODES", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY"]
 
@@ -211,6 +211,15 @@ class DrainFit(NamedTuple):
         mine = pod == int(node)
         none = np.int32(-1)
         return np.where(mine, pod, none).astype(np.int32), np.where(mine, self.target, none).astype(np.int32)
+
+
+class ScaleUp(NamedTuple):
+    """Engine.scale_up_domains' answer; a part that was not asked for is None."""
+    nodes: Optional[np.ndarray]          # int32 [P]: the fewest new nodes with which the job is placed, -1 = none up to pair_max
+    fail_group: Optional[np.ndarray]     # int32 [P]: the deciding attempt's first group not placed in full, -1 = placed
+    pods: Optional[np.ndarray]           # int64 [P]: pods the deciding attempt had placed when it stopped
+    new_pods: Optional[np.ndarray]       # int64 [P]: those of them that sit on new nodes
+    best: Optional[np.ndarray]           # int32 [J]: the pair of job j with the fewest new nodes, ties to the smallest p; -1 = none
 
 
 class GangPreempt(NamedTuple):
@@ -1055,6 +1064,47 @@ class Engine:
                                                 _p(cd), int(level), len(ls), _p(ls), _p(par), _p(o_fits), _p(o_moved),
                                                 _p(o_fail), _p(o_target)), "pe_drain_fit_domains")
         return DrainFit(o_fits, o_moved, o_fail, o_target)
+
+    def scale_up_domains(self, job_group_off, group_count, group_req, group_need, tmpl_res, tmpl_labels, new_slot,
+                         pair_job, pair_domain, pair_template, pair_max, level, level_size, parent=None, nodes=True,
+                         fail_group=True, pods=True, new_pods=True, best=True) -> ScaleUp:
+        """pe_scale_up_domains: for every pair p, the fewest nodes of template pair_template[p] (free residual
+        tmpl_res[t], labels tmpl_labels[t]) that would have to join the level-`level` domain pair_domain[p] for
+        place_greedy_domains to place job pair_job[p] ALONE there, trying 0, 1, ... pair_max[p] new nodes in that order
+        (the answer is not monotone).  The i-th new node has id new_slot[i], a removed slot of the inventory.
+        Read-only.  The batch, the pairs and the hierarchy are gang_fit_domains'; tmpl_labels None = 0, pair_max None =
+        len(new_slot) for every pair.  Each of the five answers can be left out (it then never crosses)."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        tres = _c(tmpl_res, np.int64).reshape(-1, 4)
+        tlab = None if tmpl_labels is None else _c(tmpl_labels, np.uint32).reshape(-1)
+        if tlab is not None and len(tlab) != len(tres):
+            raise ValueError("tmpl_res and tmpl_labels must have one row per template")
+        slot = _c(new_slot, np.int32).reshape(-1)
+        pj = _c(pair_job, np.int32).reshape(-1)
+        pd = _c(pair_domain, np.int32).reshape(-1)
+        pt = _c(pair_template, np.int32).reshape(-1)
+        pm = None if pair_max is None else _c(pair_max, np.int32).reshape(-1)
+        if pj.shape != pd.shape or pj.shape != pt.shape or (pm is not None and pm.shape != pj.shape):
+            raise ValueError("pair_job, pair_domain, pair_template and pair_max must have one length")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = len(pj)
+        o_nodes = np.full(P, -1, dtype=np.int32) if nodes else None
+        o_fail = np.full(P, -1, dtype=np.int32) if fail_group else None
+        o_pods = np.zeros(P, dtype=np.int64) if pods else None
+        o_new = np.zeros(P, dtype=np.int64) if new_pods else None
+        o_best = np.full(J, -1, dtype=np.int32) if best else None
+        self._chk(self.lib.pe_scale_up_domains(self.h, J, _p(jgo), _p(cnt), _p(req), _p(nd), len(tres), _p(tres), _p(tlab),
+                                               len(slot), _p(slot), P, _p(pj), _p(pd), _p(pt), _p(pm), int(level), len(ls),
+                                               _p(ls), _p(par), _p(o_nodes), _p(o_fail), _p(o_pods), _p(o_new), _p(o_best)),
+                  "pe_scale_up_domains")
+        return ScaleUp(o_nodes, o_fail, o_pods, o_new, o_best)
 
     def place_first_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
                                 pair_domain, level, level_size, parent=None, pairs=True):

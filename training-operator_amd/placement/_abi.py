@@ -31,6 +31,7 @@ PE_MAX_SPLIT_PARTS = 1024
 PE_SPLIT_TOO_MANY = -1
 PE_SLICE_NODE = -1
 PE_MAX_PAIR_VICTIMS = 64
+PE_MAX_SCALE_NODES = 64
 PE_MASK_NODE_TILES, PE_MASK_JOB_BITS, PE_MASK_NODE_BLOCKS, PE_MASK_ROWS = 0, 1, 2, 3
 HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
@@ -109,6 +110,8 @@ SIGNATURES = {
     "pe_release_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_assume_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_drain_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
+    "pe_scale_up_domains": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, i32, P, i64, P, P, P, P, i32, i32, P, P,
+                                           P, P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
     "pe_resolver_destroy": (None, [P]),
     "pe_resolver_set_nodes": (ctypes.c_int, [P, i64]),
