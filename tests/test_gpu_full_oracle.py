@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 import oracle
+from host_register import REASON as HOST_REGISTER_REASON
+from host_register import host_register_supported
 from placement import Engine, HostExchange, synth
 
 pytestmark = [pytest.mark.gpu, pytest.mark.slow]
@@ -136,6 +138,8 @@ def test_bench_greedy_batch_eight_shards_vs_oracle(bench_inv, greedy_batch, gree
     thread merges every group on the host as all 8 ranks signalled it).  Every rank's pods and job
     statuses against the ORACLE, each device shard against its slice of the oracle's residuals, and
     a second batch after pe_reset_residuals (the bench's repeated batches)."""
+    if not host_register_supported():
+        pytest.skip(HOST_REGISTER_REASON)
     inv, b = bench_inv, greedy_batch
     W = 8
     name = f"/pe_fo8_{os.getpid()}"

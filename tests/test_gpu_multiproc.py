@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import oracle
+from host_register import REASON as HOST_REGISTER_REASON
+from host_register import host_register_supported
 from placement import synth
 
 pytestmark = pytest.mark.gpu
@@ -83,6 +85,8 @@ def test_sharded_greedy_across_processes(tmp_path, world, mix, n_nodes, n_jobs, 
              "devmerge": {"PE_ZC_DEV_MERGE": "1"}, "grow": {}, "t3": {"PE_XCHG_THREADS": "3"}, "": {}}[variant]
     env = _env(**({"PE_HOST_MERGE": "1"} if host_merge else {}), **extra)
     zc_expected = base == "shm" and variant != "copy" and not host_merge
+    if zc_expected and not host_register_supported():
+        pytest.skip(HOST_REGISTER_REASON)
     transport = "shm-grow" if variant == "grow" else base
     procs = _spawn(tmp_path, world, mix, n_nodes, n_jobs, transport, env)
     outs = []
@@ -142,6 +146,8 @@ def test_zero_copy_exchange_peer_stall_fails_fast(tmp_path, dev_merge):
     """A rank that stops taking part (it sleeps, then exits) must not hang its peers: the exchange
     thread's wait for its lists gives up after PE_HX_TIMEOUT_S (PE_ZC_DEV_MERGE=1: the device wait
     after PE_HX_GPU_TIMEOUT_S) and the greedy call fails with PE_ERCCL."""
+    if not host_register_supported():
+        pytest.skip(HOST_REGISTER_REASON)
     env = _env(PE_HX_GPU_TIMEOUT_S="3", PE_HX_TIMEOUT_S="3", **({"PE_ZC_DEV_MERGE": "1"} if dev_merge else {}))
     procs = _spawn(tmp_path, 2, "mixed", 20000, 600, "shm-stall", env)
     outs = []

@@ -22,6 +22,9 @@ import time
 
 import pytest
 
+from host_register import REASON as HOST_REGISTER_REASON
+from host_register import host_register_supported
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--nodes", "100000", "--fit-jobs", "5000", "--greedy-jobs", "1000", "--agg-jobs", "20000", "--steps", "3",
@@ -61,6 +64,8 @@ def _bench(gpus, extra_env):
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_matches_one():
+    if not host_register_supported():   # (the fallback's production loop: its zero-copy windows)
+        pytest.skip(HOST_REGISTER_REASON)
     one = _bench(1, {})
     # the last rank's engine set-up fails (simulated): every rank falls back to the gloo exchange
     two = _bench(2, {"PE_BENCH_EXCHANGE": "host", "PE_BENCH_SIMULATE_RCCL_FAIL": "1", "PE_BENCH_INTERLEAVE_ONE": "1"})
