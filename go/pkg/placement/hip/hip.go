@@ -937,6 +937,37 @@ func (e *Engine) PlaceGreedyDomains(g *Gangs, jobDomain []int32, level int32, le
 	return podNode, jobStatus, e.err(rc, "pe_place_greedy_domains")
 }
 
+// SpreadNone as a cap: no cap (PE_SPREAD_NONE).  SpreadNode as a spreadLevel: the cap counts per node (PE_SPREAD_NODE).
+const (
+	SpreadNone = int32(C.PE_SPREAD_NONE)
+	SpreadNode = int32(C.PE_SPREAD_NODE)
+)
+
+// PlaceSpreadDomains is PlaceGreedyDomains with a cap on the pods of a group that one spread domain takes in this
+// call: podAntiAffinity / topologySpreadConstraints on hostname (spreadLevel SpreadNode) or on a rack key
+// (spreadLevel below level).  groupMaxPer is [G] (nil or SpreadNone: no cap); the cap counts this group's pods
+// of this call only.  dryRun answers and leaves residuals, mirror and stats as they were.  A sharded engine
+// refuses the call.
+func (e *Engine) PlaceSpreadDomains(g *Gangs, groupMaxPer []int32, spreadLevel int32, dryRun bool, jobDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	if groupMaxPer != nil && len(groupMaxPer) != len(g.GroupCount) {
+		return nil, nil, fmt.Errorf("PlaceSpreadDomains: %d caps for %d groups", len(groupMaxPer), len(g.GroupCount))
+	}
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, fmt.Errorf("PlaceSpreadDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_SPREAD_DRY_RUN
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	rc := C.pe_place_spread_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), ptr32(groupMaxPer), C.int32_t(spreadLevel), flags, ptr32(jobDomain),
+		C.int32_t(level), C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus))
+	return podNode, jobStatus, e.err(rc, "pe_place_spread_domains")
+}
+
 // MinMemberAll as a minMember: the whole job is mandatory (PE_MIN_MEMBER_ALL).
 const MinMemberAll = int32(C.PE_MIN_MEMBER_ALL)
 

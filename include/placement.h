@@ -653,6 +653,51 @@ int pe_place_min_member_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_
                                 int32_t* out_pod_node, int32_t* out_job_status,
                                 int32_t* out_group_pods /*[G] or NULL*/, int64_t* out_job_pods /*[J] or NULL*/);
 
+/* (ABI 7, additive) Gang placement with per-domain pod caps: pe_place_greedy_domains for pod templates that
+ * carry podAntiAffinity or topologySpreadConstraints on hostname or on a rack key -- parameter servers, MPI
+ * launchers, data-loader replicas, "one worker per node", "at most two replicas per rack".  The packing rule
+ * puts as many pods of a group on the argmin-key node as it holds; a cap says how many one SPREAD DOMAIN may
+ * hold.  NO reference function, as pe_place_greedy_domains.  Everything not said here means what it means in
+ * that call: jobs in (priority desc, index asc) order, groups in the given order, all-or-nothing with rollback,
+ * pod slots in group input order with GLOBAL node ids, PE_NEED_ISLAND, zero-count groups, a domain without
+ * nodes, n_jobs == 0, pe_stats and the host mirror.
+ * The spread domain sd(n) of node n is n itself when spread_level == PE_SPREAD_NODE, else dom_{spread_level}(n)
+ * with 0 <= spread_level < level (a node that has a level-`level` domain has one at every level below).
+ * The rule: group g with cap m = group_max_per[g] places its pods one at a time on the argmin-key node among
+ * the nodes of job_domain[j] that fit and whose spread domain holds fewer than m pods OF THIS GROUP FROM THIS
+ * CALL.  The cap does not count other groups' pods, other jobs' pods or pods placed by earlier calls: the engine
+ * keeps no pod book, and a caller that needs earlier pods counted lowers the cap.  A PE_NEED_ISLAND group is one
+ * unit: it needs a node whose spread domain still allows `count` pods, so with PE_SPREAD_NODE it needs
+ * m >= count.  PE_SPREAD_NONE (or group_max_per NULL) is no cap; with every group uncapped the call is
+ * pe_place_greedy_domains, output for output and residual for residual.
+ * The smallest case: a rack of two nodes with 8 free GPUs each, one group of 4 pods x 1 GPU, PE_SPREAD_NODE.
+ *   uncapped     all four pods on node 0
+ *   2 per node   nodes 0, 0, 1, 1
+ *   1 per node   PE_JOB_UNSCHEDULABLE, residuals untouched
+ * And a cap per rack: two racks of two such nodes under one block (level 1, spread_level 0), the same group.
+ *   2 per rack   nodes 0, 0, 2, 2: node 1 shares its rack with node 0, whose two pods fill the rack's cap
+ *   1 per rack   PE_JOB_UNSCHEDULABLE (two racks hold two pods)
+ * One decision on the device takes t = min(what the node holds, what its spread domain still allows, pods left)
+ * pods at once, which equals the pod-by-pod rule: a pod that lands on node n can only lower n's key and moves no
+ * other node's, so n stays the argmin until it no longer fits or its spread domain is full.
+ * flags: PE_SPREAD_DRY_RUN answers and changes nothing -- out_pod_node and out_job_status are those of the same
+ * call without the flag (later jobs of a domain see earlier jobs' takes), while the device residuals, the host
+ * mirror and pe_stats stay as they were: a read-only what-if of a whole batch.
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there is
+ * one): everything pe_place_greedy_domains refuses, spread_level < -1 or >= level, a group_max_per[g] of 0 or
+ * below -1, unknown flags bits, world_size > 1.  PE_ESTATE: a call before pe_load_nodes. */
+#define PE_SPREAD_NONE (-1)      /* group_max_per[g]: no cap */
+#define PE_SPREAD_NODE (-1)      /* spread_level: the cap counts per node */
+#define PE_SPREAD_DRY_RUN 1u     /* flags: answer, change nothing */
+int pe_place_spread_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                            const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                            const int32_t* group_max_per /*[G], or NULL = every group PE_SPREAD_NONE*/,
+                            int32_t spread_level, uint32_t flags,
+                            const int32_t* job_domain /*[J]*/, int32_t level,
+                            int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                            const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                            int32_t* out_pod_node, int32_t* out_job_status);
+
 /* (ABI 7, additive) Exact what-if of a whole gang per domain: would this job, all its groups in order, be
  * placed in this domain right now?  The read-only link between pe_gang_capacity_tree (which domains hold a
  * gang of ONE shape) and pe_place_greedy_domains (which places the gang and changes the residuals).  For a

@@ -63,6 +63,16 @@ void raise_fit_plan(pe::FitPlanError e, pe::TreePlanError te, int64_t bad) {
   }
 }
 
+void raise_place_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad) {
+  switch (e) {
+    case pe::PLACE_BAD_LEVEL: raise(PE_EINVAL, "level outside [0, n_levels)");
+    case pe::PLACE_NO_DOMAINS: raise(PE_EINVAL, "job_domain is NULL");
+    case pe::PLACE_BAD_DOMAIN:
+      raise(PE_EINVAL, "job_domain: value outside [0, level_size[level]) at index " + std::to_string(bad));
+    default: raise_tree(te, bad);   // the hierarchy, in pe_gang_capacity_tree's words
+  }
+}
+
 void fill_place_groups(pe::PlaceGroup* out, int64_t G, const int64_t* group_req, const uint32_t* group_need,
                        const int32_t* count, const int64_t* pod0) {
   for (int64_t g = 0; g < G; ++g) {

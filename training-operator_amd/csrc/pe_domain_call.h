@@ -7,6 +7,7 @@
 
 #include "pe_ctx.h"
 #include "pe_fit_plan.h"
+#include "pe_place_plan.h"
 
 namespace pe_engine {
 
@@ -14,6 +15,9 @@ namespace pe_engine {
 void domain_entry_checks(const pe_ctx* ctx, const char* call, int64_t n_jobs);
 // A refused pair list (pe_fit_plan.h FitPlanError, `bad` its index), the hierarchy in raise_tree's words.
 [[noreturn]] void raise_fit_plan(pe::FitPlanError e, pe::TreePlanError te, int64_t bad);
+
+// A refused placing plan (pe_place_plan.h PlacePlanError, `bad` its index), the hierarchy in raise_tree's words.
+[[noreturn]] void raise_place_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad);
 
 inline size_t r16(size_t x) { return (x + 15) & ~size_t(15); }
 

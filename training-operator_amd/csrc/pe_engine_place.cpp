@@ -11,16 +11,6 @@
 
 namespace {
 
-[[noreturn]] void raise_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad) {
-  switch (e) {
-    case pe::PLACE_BAD_LEVEL: raise(PE_EINVAL, "level outside [0, n_levels)");
-    case pe::PLACE_NO_DOMAINS: raise(PE_EINVAL, "job_domain is NULL");
-    case pe::PLACE_BAD_DOMAIN:
-      raise(PE_EINVAL, "job_domain: value outside [0, level_size[level]) at index " + std::to_string(bad));
-    default: raise_tree(te, bad);   // the hierarchy, in pe_gang_capacity_tree's words
-  }
-}
-
 // An entry's names in its errors.  min: pe_place_min_member_domains -- the plan of pe_place_min_plan.h, the groups'
 // MANDATORY shares as their records with every group's optional share beside them, PlaceMinJob records, a log of
 // the mandatory pods only and one more block of the answer (the groups' placed pods).  min_member, out_group_pods
@@ -60,7 +50,7 @@ int place_in_domains(pe_ctx* ctx, const Entry& en, int64_t n_jobs, const int32_t
       be = pe::place_plan_build(mp.base, n_jobs, job_group_off, priority, group_count, job_domain, level, n_levels,
                                 level_size, parent, &te, &bad);
     }
-    if (be != pe::PLACE_OK) raise_plan(be, te, bad);
+    if (be != pe::PLACE_OK) raise_place_plan(be, te, bad);
     if (n_jobs == 0) return PE_OK;
 
     const pe::PlacePlan& plan = mp.base;

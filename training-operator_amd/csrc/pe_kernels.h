@@ -638,6 +638,23 @@ hipError_t launch_place_min_domains(hipStream_t s, const PlaceGroup* groups, con
                                     int64_t* res, int64_t stride, uint64_t id_base, int32_t* out_pod, int32_t* out_status,
                                     int32_t* out_group_pods, int32_t* log);
 
+// ---- gang placement with per-domain pod caps (pe_place_spread_domains, pe_spread.hip; the plan:
+// pe_spread_plan.h).  The working state of a place grows by its allowance (4 B: 44 B per place) when the spread
+// domain is the node, and by the allowance and its spread domain's rank (48 B) when it is a domain of a lower
+// level.  Each kind has its own kernel instance and its own LDS limit, the largest segment that keeps the workgroup
+// within the 40 KiB of PL_LDS_NODES' comment: 928 x 44 B + 128 B = 40 960 B, 850 x 48 B + 128 B = 40 928 B.
+constexpr int SP_LDS_NODES_NODE = 928;
+constexpr int SP_LDS_NODES_DOM = 850;
+// launch_place_domains with caps[G] (>= 1 each; INT32_MAX: no cap) counted per spread domain.  leaf_sub == NULL: the
+// spread domain is the node; else leaf_sub[n_leaf] is the plan's (island [Ns]: the nodes' leaves) and sub_row
+// [seg_stride] receives every place's rank.  allow_row [seg_stride]: scratch.  dry_run: out_pod and out_status as
+// without it, res left as it is.  The member lists are launch_place_members'.
+hipError_t launch_spread_domains(hipStream_t s, const PlaceGroup* groups, const int32_t* caps, const PlaceJob* jobs,
+                                 const int32_t* job_start, int A, const PlaceSegs& segs, const int32_t* island, int64_t Ns,
+                                 const int32_t* leaf_sub, uint32_t* allow_row, uint32_t* sub_row, int64_t* res,
+                                 int64_t stride, uint64_t id_base, bool dry_run, int32_t* out_pod, int32_t* out_status,
+                                 int32_t* log);
+
 // ---- first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_place.hip; the plan:
 // pe_first_fit_plan.h).  The member lists are launch_place_members'; the segments stay the working residuals of
 // their domains from round to round.
