@@ -1086,6 +1086,41 @@ func (e *Engine) GangPreemptDomains(g *Gangs, v *Victims, pairJob, pairDomain, p
 	return prefix, victims, count, best, e.err(rc, "pe_gang_preempt_domains")
 }
 
+// PlacePreemptDomains is PlaceGreedyDomains for a batch whose jobs may evict (pe_place_preempt_domains): job j comes
+// with the candidate victims jobVic[jobVicOff[j]:jobVicOff[j+1]] in eviction order, indices into v.  Within a domain,
+// in (priority desc, index asc) order, each job is placed if it fits, else after the smallest prefix of its
+// still-live candidates whose release places it, less those the fill-back returns; later jobs see what earlier jobs
+// left, and a victim an earlier job evicted is dead in every later list.  prefix[j] is that prefix (-1: the job is
+// unschedulable and evicts nobody), victims[j] the evicted list positions (bit i = position i), vicJob[k] the job
+// that evicted victim k or -1.  Residuals are updated in place: the placements come off and every evicted gang goes
+// back whole.  dryRun answers the same and leaves residuals, mirror and stats as they were.  A sharded engine
+// refuses the call.
+func (e *Engine) PlacePreemptDomains(g *Gangs, jobDomain []int32, level int32, levelSize, parent []int32, v *Victims, jobVicOff, jobVic []int32, dryRun bool) (podNode, jobStatus, prefix []int32, victims []uint64, vicJob []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	V := len(v.GroupOff) - 1
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, nil, nil, nil, fmt.Errorf("PlacePreemptDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	if len(jobVicOff) != J+1 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("PlacePreemptDomains: %d list offsets for %d jobs", len(jobVicOff), J)
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_PREEMPT_DRY_RUN
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	prefix = make([]int32, J)
+	victims = make([]uint64, J)
+	vicJob = make([]int32, V)
+	rc := C.pe_place_preempt_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), ptr32(jobDomain), C.int32_t(level), C.int32_t(len(levelSize)),
+		ptr32(levelSize), ptr32(parent), C.int64_t(V), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq),
+		ptr32(v.PodNode), ptr32(jobVicOff), ptr32(jobVic), flags, ptr32(podNode), ptr32(jobStatus), ptr32(prefix),
+		ptru64(victims), ptr32(vicJob))
+	return podNode, jobStatus, prefix, victims, vicJob, e.err(rc, "pe_place_preempt_domains")
+}
+
 // ReleaseGangs gives back what placed gangs hold (pe_release_gangs): every pod slot of v on a node that is not a
 // removed slot adds its group's request to the node's residuals; -1 slots count nothing, so the arguments and
 // outputs of a placement call -- an Unreserve, or the victims GangPreemptDomains names -- can be handed straight

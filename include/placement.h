@@ -899,6 +899,68 @@ int pe_assume_gangs(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off 
                     const int32_t* pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
                     int64_t* out_pods /* or NULL */);
 
+/* (ABI 7, additive) Place a batch, evicting as it goes: the batch form of the chain pe_gang_preempt_domains ->
+ * pe_release_gangs -> pe_place_greedy_domains, which is exact for one job at a time only (two jobs may both be told
+ * "evict gang 12", and the second answer is stale once the first job is placed).  This is what Volcano's preempt
+ * action and the kube-scheduler's PostFilter run: jobs in priority order, each placed if it fits, otherwise placed
+ * after evicting the fewest of its candidate victims, later jobs seeing what earlier jobs left.  NO reference
+ * function, as pe_place_greedy_domains.
+ * Jobs, groups, job_domain, level and hierarchy, out_pod_node and out_job_status mean what they mean in
+ * pe_place_greedy_domains; the victims (vic_*) mean what they mean in pe_gang_preempt_domains and pe_release_gangs.
+ * Job j's candidates are job_vic[job_vic_off[j] .. job_vic_off[j + 1]), K_j of them, at most PE_MAX_PAIR_VICTIMS,
+ * in eviction order.  Which gangs a job may evict is the caller's policy: the engine compares no priorities
+ * between jobs and victims.
+ * The rule.  Within a domain, jobs are handled in (priority desc, index asc) order.  A victim is DEAD once an
+ * earlier job of the call has evicted it; a dead position of a list releases nothing and is never reported.  For
+ * job j with domain D:
+ *   Phase 1   the prefixes k = 0 .. K_j are tried in ascending order; k is judged only when k = 0 or position
+ *             k - 1 is live.  A judgement at k is pe_place_greedy_domains of the single job in D against the
+ *             residuals as the earlier jobs left them, after every pod of the live positions below k whose node n
+ *             has dom_level(n) == D gave its request back (pe_gang_preempt_domains' R(E)).  out_job_prefix[j] is the
+ *             first k that places the job, -1 when none does.
+ *   Phase 2   (only when k >= 2)  E = the live positions below k; for i = k - 2 down to 0, live positions only: if
+ *             the job is placed against R(E \ {i}) then E := E \ {i}.  Position k - 1 is never tried.
+ *   Commit    the victims of E are evicted and the job stands exactly as the judgement against R(E) placed it.
+ *             out_job_victims[j] = E as a bit mask over list positions, out_vic_job[v] = the job that evicted
+ *             victim v, or -1.  With prefix -1 the job is PE_JOB_UNSCHEDULABLE, its slots hold -1, nothing of it
+ *             remains and none of its candidates is evicted.
+ *   Outside   an evicted gang leaves whole: its pods outside D (and not on removed slots) are given back too, but
+ *             only after every job of the call is decided -- no job of the call sees those resources; when the call
+ *             returns, the device residuals and the mirror hold them.
+ * A job costs at most (live K_j + 1) + max(0, k - 1) judgements.
+ * flags: PE_PREEMPT_DRY_RUN -- every output is that of the same call without the flag; residuals, mirror and
+ * pe_stats are untouched.
+ * Three identities: with empty lists, outputs and residuals equal pe_place_greedy_domains'; with one job in the
+ * call, out_job_prefix and out_job_victims equal pe_gang_preempt_domains' out_prefix and out_victims for the pair
+ * (job, job_domain) with the same list; and pe_release_gangs of the placed jobs followed by pe_assume_gangs of the
+ * evicted victims brings the residuals back bit-equal to those before the call.
+ * The example: one rack holds n0 and n1 with 8 GPUs each, all taken by A (4 GPUs, n0), B (4 GPUs, n0) and C (8
+ * GPUs, n1).  Job 0 (priority 10, one pod x 8 GPUs, list [A, C, B]): prefixes 0 and 1 fail, prefix 2 places it on
+ * n1, phase 2 drops A -- mask 0b010, prefix 2, out_vic_job[C] = 0.  Job 1 (priority 5, one pod x 4 GPUs, list
+ * [C, A]): prefix 0 fails, position 0 is dead so prefix 1 is not judged, prefix 2 places it on n0 -- mask 0b10,
+ * prefix 2, out_vic_job[A] = 1.  Both nodes end with 0 free and B stays.
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there is
+ * one): everything pe_place_greedy_domains refuses; everything pe_gang_preempt_domains refuses about the victims
+ * and about a list (length, range, a victim twice in one list); a victim named in the lists of jobs of two
+ * different domains (a victim belongs to one workgroup); unknown flags bits; world_size > 1; and the release
+ * bound: whatever pe_release_gangs of ALL the call's victims as one call would refuse against the reset snapshot
+ * (products and sums in 128 bits), after which no subset's release can cross the snapshot or wrap.  PE_ESTATE: a
+ * call before pe_load_nodes.  n_jobs == 0 is PE_OK (out_vic_job all -1).  out_job_prefix, out_job_victims and
+ * out_vic_job may be NULL. */
+#define PE_PREEMPT_DRY_RUN 1u    /* flags: answer, change nothing */
+int pe_place_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                             const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                             const int32_t* job_domain /*[J]*/, int32_t level, int32_t n_levels,
+                             const int32_t* level_size /*[n_levels]*/,
+                             const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                             int64_t n_victims, const int32_t* vic_group_off /*[V+1]*/,
+                             const int32_t* vic_group_count /*[VG]*/, const int64_t* vic_group_req /*[VG][4]*/,
+                             const int32_t* vic_pod_node /*[sum of counts]: global node id per pod slot, -1 = skipped*/,
+                             const int32_t* job_vic_off /*[J+1]*/, const int32_t* job_vic /* victim indices, eviction order */,
+                             uint32_t flags, int32_t* out_pod_node, int32_t* out_job_status,
+                             int32_t* out_job_prefix /*[J] or NULL*/, uint64_t* out_job_victims /*[J] or NULL*/,
+                             int32_t* out_vic_job /*[V] or NULL*/);
+
 /* (ABI 7, additive) Why a pod shape fits no node, counted per reason: the numbers behind the Unschedulable
  * condition a gang scheduler owes its users on the PodGroup and the job -- kube-scheduler's "0/5000 nodes are
  * available: 3200 Insufficient amd.com/gpu, 1800 node(s) didn't match ..." -- and behind the two decisions

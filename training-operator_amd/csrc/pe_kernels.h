@@ -753,6 +753,45 @@ hipError_t launch_preempt_place_map(hipStream_t s, const PlaceSegs& segs, int A,
 hipError_t launch_preempt(hipStream_t s, const PreIn& in, int64_t blocks, const FitLarge* large, int64_t* scratch,
                           const PlaceSegs& segs, const PreOut& out);
 
+// ---- place a batch, evicting as it goes (pe_place_preempt_domains, pe_place_preempt.hip; the plan:
+// pe_place_preempt_plan.h; release records as for the preempt call).  The member lists are launch_place_members',
+// the place map launch_preempt_place_map's.
+struct PreemptJob;   // one job in plan order (pe_place_preempt_plan.h)
+// What the kernels read besides the segments.  vic_act[V]: the active domain whose jobs list victim v, -1 = no job
+// does; node_place as PreIn's.
+struct PlacePreIn {
+  const PlaceGroup* groups;
+  const PreemptJob* jobs;
+  const int32_t* job_start;   // [A + 1]
+  const int32_t* list;        // the caller's job_vic
+  const int32_t* rec_start;   // [V + 1]
+  const PreRec* recs;
+  const int32_t* vic_act;
+  const int32_t* node_place;
+  int64_t Ns;
+  uint64_t id_base;
+};
+// The answers of a call, on the device: pod [P], and by the caller's job index status, prefix and victims; vic_job
+// [V] (the caller sets every cell to -1; the workgroup that owns a victim also reads it: a cell >= 0 is a DEAD
+// victim) and attempts (one cell the caller zeroes: placements tried).
+struct PlacePreOut {
+  int32_t* pod;
+  int32_t* status;
+  int32_t* prefix;
+  uint64_t* victims;
+  int32_t* vic_job;
+  unsigned long long* attempts;
+};
+// One workgroup per active domain a < A, as launch_place_domains: its jobs in plan order through the two phases on
+// the segment as the earlier jobs left it.  log: 3 int32 of scratch per pod slot.  dry_run: the answers alone, res
+// left as it is; else the segments' residuals go back to res.
+hipError_t launch_place_preempt(hipStream_t s, const PlacePreIn& in, int A, const PlaceSegs& segs, int64_t* res,
+                                int64_t stride, bool dry_run, const PlacePreOut& out, int32_t* log);
+// After it (not for a dry run): every record of an evicted victim (vic_job >= 0) whose node lies outside its active
+// domain's segment and is not a removed slot goes back to res.
+hipError_t launch_place_preempt_sweep(hipStream_t s, const PlacePreIn& in, int64_t V, const PlaceSegs& segs,
+                                      const int32_t* vic_job, int64_t* res, int64_t stride);
+
 // ---- giving back and re-taking placed gangs (pe_release_gangs, pe_assume_gangs, pe_ledger.hip)
 constexpr int LG_THREADS = 256;       // threads per block
 constexpr int LG_MAX_BLOCKS = 256;    // one block per CU; beyond LG_THREADS x LG_MAX_BLOCKS records the grid strides

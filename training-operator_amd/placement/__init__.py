@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SCALE_NODES, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
-                   PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_SPREAD_DRY_RUN,
+                   PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_PREEMPT_DRY_RUN, PE_SPREAD_DRY_RUN,
                    PE_SPREAD_NODE, PE_SPREAD_NONE)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -28,7 +28,7 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "ScaleUp", "PE_MAX_SCALE_NODES", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY",
-           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN"]
+           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN"]
 
 
 class PlacementError(RuntimeError):
@@ -230,6 +230,15 @@ class GangPreempt(NamedTuple):
     victims: Optional[np.ndarray]        # uint64 [P]: the final set after the fill-back, bit i = position i of the list
     count: Optional[np.ndarray]          # int32 [P]: its popcount, -1 when the prefix is -1
     best: Optional[np.ndarray]           # int32 [J]: the pair of job j with the smallest count >= 0, ties to the smallest p; -1 = none
+
+
+class PlacePreempt(NamedTuple):
+    """Engine.place_preempt_domains' answer."""
+    pod_node: np.ndarray                 # int32 [P]: the node of every pod slot, -1 in the slots of a job that is not placed
+    status: np.ndarray                   # int32 [J]: PE_JOB_PLACED / PE_JOB_UNSCHEDULABLE
+    prefix: np.ndarray                   # int32 [J]: the first prefix of the job's list that placed it, -1 = none
+    victims: np.ndarray                  # uint64 [J]: the positions of its list that it evicted, bit i = position i
+    vic_job: np.ndarray                  # int32 [V]: the job that evicted victim v, -1 = nobody
 
 
 def _level_sizes(level_size):
@@ -1032,6 +1041,50 @@ class Engine:
                                                    len(ls), _p(ls), _p(par), _p(prefix), _p(victims), _p(count), _p(bst)),
                   "pe_gang_preempt_domains")
         return GangPreempt(prefix, victims, count, bst)
+
+    def place_preempt_domains(self, job_group_off, priority, group_count, group_req, group_need, job_domain, level,
+                              level_size, parent, vic_group_off, vic_group_count, vic_group_req, vic_pod_node,
+                              job_vic_off, job_vic, dry_run=False) -> PlacePreempt:
+        """pe_place_preempt_domains: place_greedy_domains for a batch whose jobs may evict.  Job j comes with the
+        candidate victims job_vic[job_vic_off[j] .. job_vic_off[j + 1]) in eviction order (indices into the victims,
+        which are gang_preempt_domains': vic_group_off [V + 1], vic_group_count, vic_group_req, vic_pod_node).  In
+        (priority desc, index asc) order within a domain each job is placed if it fits, else after the smallest
+        prefix of its still-live candidates whose release places it, less those the fill-back returns; later jobs
+        see what earlier jobs left.  Residuals are updated in place: the placements come off, every evicted gang
+        goes back whole.  dry_run: the same answer, with residuals, mirror and stats left as they were."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        dom = None if job_domain is None else _c(job_domain, np.int32)
+        if dom is not None and dom.shape != (J,):
+            raise ValueError("job_domain must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        vgo = _c(vic_group_off, np.int32).reshape(-1)
+        V = len(vgo) - 1
+        vcnt = _c(vic_group_count, np.int32).reshape(-1)
+        vreq = _c(vic_group_req, np.int64).reshape(-1, 4)
+        vpn = None if vic_pod_node is None else _c(vic_pod_node, np.int32).reshape(-1)
+        jvo = _c(job_vic_off, np.int32).reshape(-1)
+        if len(jvo) != J + 1:
+            raise ValueError("job_vic_off must be [J + 1]")
+        jv = _c(job_vic, np.int32).reshape(-1)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        prefix = np.full(max(J, 1), -1, dtype=np.int32)
+        mask = np.zeros(max(J, 1), dtype=np.uint64)
+        vjob = np.full(max(V, 1), -1, dtype=np.int32)
+        self._chk(self.lib.pe_place_preempt_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req), _p(nd),
+                                                    _p(dom), int(level), len(ls), _p(ls), _p(par), V, _p(vgo), _p(vcnt),
+                                                    _p(vreq), _p(vpn), _p(jvo), _p(jv),
+                                                    PE_PREEMPT_DRY_RUN if dry_run else 0, _p(pod), _p(st), _p(prefix),
+                                                    _p(mask), _p(vjob)), "pe_place_preempt_domains")
+        return PlacePreempt(pod[:P], st[:J], prefix[:J], mask[:J], vjob[:V])
 
     def _ledger(self, fn, what, gang_group_off, group_count, group_req, pod_node) -> int:
         off = _c(gang_group_off, np.int32).reshape(-1)
