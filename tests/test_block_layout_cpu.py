@@ -1,0 +1,18 @@
+"""The layout of the domain calls' pinned blocks (csrc/pe_block.h) on the CPU: tests/cpp/test_block_layout.cc, a
+stand-alone program compiled here with the address and undefined-behaviour sanitizers and run directly."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "test_block_layout.cc")
+INC = os.path.join(ROOT, "training-operator_amd", "csrc")
+
+
+def test_block_layout_offsets_spans_and_alignment(tmp_path):
+    exe = tmp_path / "test_block_layout"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wall", "-Wextra", "-Werror", "-I", INC, SRC, "-o", str(exe)], check=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "66 checks, 0 failures" in p.stdout, p.stdout
+    assert "FAIL" not in p.stdout and "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr

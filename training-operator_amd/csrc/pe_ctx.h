@@ -414,8 +414,8 @@ struct pe_ctx {
   // reads back is written by its kernels or preset by its own memsets -- so calls of any shape may alternate with
   // each other and with every other entry point; nothing of a hierarchy, a batch, a pair list or a victim list
   // outlives a call.  Grow and are reused.
-  HostBuf<uint8_t> dm_hin;      // one copy in: the call's own block, G PlaceGroup first, the plan's words last (each
-  DevBuf<uint8_t> dm_in;        // unit's *_at offsets)
+  HostBuf<uint8_t> dm_hin;      // one copy in: the call's own block, G PlaceGroup first (each unit states its parts as
+  DevBuf<uint8_t> dm_in;        // a pe_block.h layout; pe_domain_call.h's buffer steps size and copy by it)
   DevBuf<uint8_t> dm_out;       // one copy out: the call's answers, again in its own layout
   HostBuf<uint8_t> dm_hout;
   DevBuf<int32_t> dm_log;       // the placing calls' rollback logs, [pods][3]

@@ -91,6 +91,40 @@ int32_t* pack_domain_words(int32_t* out, const std::vector<int32_t>& leaf_dom, c
   return out + leaf_dom.size() + act_of.size();
 }
 
+static void blockchk(hipError_t e, const char* before, const char* noun, const char* after) {
+  if (e != hipSuccess) hipchk(e, (std::string(before) + noun + after).c_str());   // the words only for an error
+}
+
+uint8_t* block_in_host(pe_ctx* ctx, const pe::BlockLayout& in, const char* noun) {
+  blockchk(ctx->dm_hin.ensure(in.bytes()), "alloc pinned ", noun, " inputs");
+  blockchk(ctx->dm_in.ensure(in.bytes()), "alloc ", noun, " inputs");
+  return ctx->dm_hin.p;
+}
+
+const uint8_t* block_in_device(pe_ctx* ctx, const pe::BlockLayout& in, const char* noun) {
+  const hipError_t e = hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in.bytes(), hipMemcpyHostToDevice, ctx->stream);
+  blockchk(e, "H2D ", noun, " inputs");
+  return ctx->dm_in.p;
+}
+
+uint8_t* block_out_device(pe_ctx* ctx, const pe::BlockLayout& out, const char* noun, bool whole) {
+  blockchk(ctx->dm_out.ensure(out.bytes()), "alloc ", noun, " outputs");
+  if (whole) blockchk(ctx->dm_hout.ensure(out.bytes()), "alloc pinned ", noun, " outputs");
+  return ctx->dm_out.p;
+}
+
+const uint8_t* block_read_back(pe_ctx* ctx, const pe::BlockLayout& out, const char* noun, const char* sync,
+                               const char* d2h) {
+  if (out.any) {
+    blockchk(ctx->dm_hout.ensure(out.hi), "alloc pinned ", noun, " outputs");
+    const hipError_t e = hipMemcpyAsync(ctx->dm_hout.p + out.lo, ctx->dm_out.p + out.lo, out.hi - out.lo,
+                                        hipMemcpyDeviceToHost, ctx->stream);
+    d2h ? hipchk(e, d2h) : blockchk(e, "D2H ", noun, " answers");
+  }
+  hipchk(hipStreamSynchronize(ctx->stream), sync);
+  return ctx->dm_hout.p;
+}
+
 pe::PlaceSegs domain_segments(pe_ctx* ctx, int64_t A) {
   const int64_t st = std::max<int64_t>(ctx->stride, 1);
   hipchk(ctx->dm_dom.ensure((size_t)(3 * A + 1)), "alloc domain lists");

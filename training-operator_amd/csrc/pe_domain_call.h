@@ -1,10 +1,12 @@
-// libplacement: the host scaffold of the domain calls (pe_place_greedy_domains, pe_place_min_member_domains,
-// pe_gang_fit_domains, pe_place_first_fit_domains, pe_gang_preempt_domains; pe_domain_call.cpp).  Each of them
-// validates, builds its plan, packs one pinned block, gathers every active domain's nodes into segments, launches
-// and copies back once; what is the same in all of them is here, on the one buffer set pe_ctx.h dm_*.  Calls on a
+// libplacement: the host scaffold of the domain calls (pe_place_*_domains, pe_gang_fit_domains,
+// pe_gang_preempt_domains, pe_drain_fit_domains, pe_scale_up_domains; pe_domain_call.cpp).  Each of them validates,
+// builds its plan, packs one pinned block, gathers every active domain's nodes into segments, launches and copies
+// back once; what is the same in all of them is here, on the one buffer set pe_ctx.h dm_*.  A call states the parts of
+// its block in and of its block out once, as layouts (pe_block.h); the buffer steps below work by them.  Calls on a
 // context are serialised (guarded), and every call sizes and fills what it reads, so one set serves them all.
 #pragma once
 
+#include "pe_block.h"
 #include "pe_ctx.h"
 #include "pe_fit_plan.h"
 #include "pe_place_plan.h"
@@ -19,7 +21,27 @@ void domain_entry_checks(const pe_ctx* ctx, const char* call, int64_t n_jobs);
 // A refused placing plan (pe_place_plan.h PlacePlanError, `bad` its index), the hierarchy in raise_tree's words.
 [[noreturn]] void raise_place_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad);
 
-inline size_t r16(size_t x) { return (x + 15) & ~size_t(15); }
+// The buffer steps of a call, by its layouts; `noun` names the call in the errors' words ("alloc pinned gang-fit
+// inputs", "H2D gang-fit inputs", "alloc gang-fit outputs", "D2H gang-fit answers").  In: dm_hin and dm_in sized, the
+// pinned base to fill; then the one copy in queued, the device base.  Out: dm_out sized -- and dm_hout, where the call
+// reads all of it back (whole) --, the device base; then the one copy out of the wanted span, into dm_hout sized up
+// to its end (nothing where nothing is wanted; d2h: the copy's words where they are not the noun's), and the call's
+// synchronisation in the words of `sync`: the pinned base.
+uint8_t* block_in_host(pe_ctx* ctx, const pe::BlockLayout& in, const char* noun);
+const uint8_t* block_in_device(pe_ctx* ctx, const pe::BlockLayout& in, const char* noun);
+uint8_t* block_out_device(pe_ctx* ctx, const pe::BlockLayout& out, const char* noun, bool whole = false);
+const uint8_t* block_read_back(pe_ctx* ctx, const pe::BlockLayout& out, const char* noun, const char* sync,
+                               const char* d2h = nullptr);
+// One part of the answer to the caller, where the caller gave a pointer.
+template <class T, class U>
+void block_part_to(U* dst, const pe::BlockPart<T>& part, const uint8_t* host) {
+  static_assert(sizeof(T) == sizeof(U), "the answer's cells are the caller's");
+  if (dst && part.count > 0) std::memcpy(dst, host + part.at, part.bytes());
+}
+// The 64-bit best cells to the caller's pairs: the low half of the minimum is the pair; ~0 reads as -1: no answer.
+inline void block_best_to(int32_t* dst, const pe::BlockPart<unsigned long long>& best, const uint8_t* host) {
+  for (size_t j = 0; dst && j < best.count; ++j) dst[j] = (int32_t)(uint32_t)best.in(host)[j];
+}
 
 // G zero-filled records from the caller's arrays: need 0 where group_need is NULL, pod0 0 where pod0 is NULL.
 void fill_place_groups(pe::PlaceGroup* out, int64_t G, const int64_t* group_req, const uint32_t* group_need,

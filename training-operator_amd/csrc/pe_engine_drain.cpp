@@ -73,54 +73,48 @@ int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group
     }
     const int64_t L0 = plan.fit.n_leaf, ND = plan.fit.n_dom;
     // ---- one pinned block in: the runs, the candidates in plan order, the units, the plan's words, the slot lists
-    const size_t pairs_at = (size_t)R * sizeof(pe::PlaceGroup);
-    const size_t units_at = pairs_at + (size_t)C * sizeof(pe::DrainPair);
-    const size_t words_at = units_at + (size_t)U * sizeof(pe::FitUnit);
-    const size_t slots_at = words_at + (size_t)(L0 + ND) * sizeof(int32_t);
-    const size_t in_bytes = slots_at + (size_t)E * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned drain-fit inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc drain-fit inputs");
-    pe::PlaceGroup* const h_runs = (pe::PlaceGroup*)ctx->dm_hin.p;
+    pe::BlockLayout in;
+    const auto runs = in.add<pe::PlaceGroup>(R);
+    const auto pairs = in.add<pe::DrainPair>(C);
+    const auto units = in.add<pe::FitUnit>(U);
+    const auto words = in.add<int32_t>(L0 + ND);
+    const auto slots = in.add<int32_t>(E);
+    uint8_t* const h = block_in_host(ctx, in, "drain-fit");
     for (int64_t r = 0; r < R; ++r) {
       const pe::DrainRun& run = plan.runs[(size_t)r];
-      pe::PlaceGroup& o = h_runs[r];
+      pe::PlaceGroup& o = runs.in(h)[r];
       std::memset(&o, 0, sizeof(o));
       for (int d = 0; d < pe::D; ++d) o.q[d] = group_req[(int64_t)run.group * pe::D + d];
       o.need = group_need ? group_need[run.group] : 0u;
       o.count = run.count;
       o.pod0 = run.pod0;
     }
-    pe::DrainPair* const h_pairs = (pe::DrainPair*)(ctx->dm_hin.p + pairs_at);
+    pe::DrainPair* const h_pairs = pairs.in(h);
     for (int64_t i = 0; i < C; ++i) {
       const int32_t c = plan.fit.pairs[(size_t)i];
       h_pairs[i] = pe::DrainPair{c, cand_node[c], plan.run_start[(size_t)c], plan.run_start[(size_t)c + 1]};
     }
-    std::memcpy(ctx->dm_hin.p + units_at, plan.fit.units.data(), (size_t)U * sizeof(pe::FitUnit));
-    pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), plan.fit.leaf_dom, plan.fit.act_of);
-    std::memcpy(ctx->dm_hin.p + slots_at, plan.slot_list.data(), (size_t)E * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D drain-fit inputs");
-    const pe::PlaceGroup* const d_runs = (const pe::PlaceGroup*)ctx->dm_in.p;
-    const pe::DrainPair* const d_pairs = (const pe::DrainPair*)(ctx->dm_in.p + pairs_at);
-    const pe::FitUnit* const d_units = (const pe::FitUnit*)(ctx->dm_in.p + units_at);
-    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
-    const int32_t* const d_slots = (const int32_t*)(ctx->dm_in.p + slots_at);
+    std::memcpy(units.in(h), plan.fit.units.data(), units.bytes());
+    pack_domain_words(words.in(h), plan.fit.leaf_dom, plan.fit.act_of);
+    std::memcpy(slots.in(h), plan.slot_list.data(), slots.bytes());
+    const uint8_t* const d = block_in_device(ctx, in, "drain-fit");
     // ---- the call's device buffers; the answers: fits, moved and fail_slot [C], then target [S], 16-B aligned
     const bool store = out_target != nullptr;
-    const size_t moved_at = r16((size_t)C);
-    const size_t fail_at = moved_at + r16((size_t)C * sizeof(int64_t));
-    const size_t target_at = fail_at + r16((size_t)C * sizeof(int64_t));
-    const size_t out_bytes = target_at + (store ? (size_t)S * sizeof(int32_t) : 0);
-    hipchk(ctx->dm_out.ensure(out_bytes), "alloc drain-fit outputs");
+    pe::BlockLayout ans;
+    const auto fits = ans.add<uint8_t>(C, 16, out_fits != nullptr);
+    const auto moved = ans.add<int64_t>(C, 16, out_moved != nullptr);
+    const auto fail = ans.add<int64_t>(C, 16, out_fail_slot != nullptr);
+    const auto target = ans.add<int32_t>(store ? S : 0, 16, store);
+    uint8_t* const o = block_out_device(ctx, ans, "drain-fit");
     const pe::PlaceSegs segs = domain_segments(ctx, A);
-    pe::DrainOut out{ctx->dm_out.p, (int64_t*)(ctx->dm_out.p + moved_at), (int64_t*)(ctx->dm_out.p + fail_at),
-                     store ? (int32_t*)(ctx->dm_out.p + target_at) : nullptr};
-    if (store) hipchk(hipMemsetAsync(out.target, 0xFF, (size_t)S * sizeof(int32_t), ctx->stream), "clear targets");
+    pe::DrainOut out{fits.in(o), moved.in(o), fail.in(o), store ? target.in(o) : nullptr};
+    if (store) hipchk(hipMemsetAsync(out.target, 0xFF, target.bytes(), ctx->stream), "clear targets");
     CapEvents ev(ctx);
     ev.begin();
-    launch_domain_members(ctx, d_words, L0, A, segs);
+    launch_domain_members(ctx, words.in(d), L0, A, segs);
     const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
-      hipchk(pe::launch_drain(ctx->stream, d_runs, d_pairs, d_units, blocks, large.recs, large.scratch, d_slots, segs, out,
-                              store),
+      hipchk(pe::launch_drain(ctx->stream, runs.in(d), pairs.in(d), units.in(d), blocks, large.recs, large.scratch,
+                              slots.in(d), segs, out, store),
              what);
     };
     launch_units_then_large(
@@ -128,22 +122,11 @@ int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group
         [&](const LargeSegs& large) { launch(large.n, large, "launch drain_domains (global)"); });
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for
-    const size_t lo = out_fits ? 0 : out_moved ? moved_at : out_fail_slot ? fail_at : target_at;
-    const size_t hi = out_target      ? out_bytes
-                      : out_fail_slot ? fail_at + (size_t)C * sizeof(int64_t)
-                      : out_moved     ? moved_at + (size_t)C * sizeof(int64_t)
-                                      : (size_t)C;
-    if (out_fits || out_moved || out_fail_slot || out_target) {
-      hipchk(ctx->dm_hout.ensure(hi), "alloc pinned drain-fit outputs");
-      hipchk(hipMemcpyAsync(ctx->dm_hout.p + lo, ctx->dm_out.p + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream),
-             "D2H drain-fit answers");
-    }
-    hipchk(hipStreamSynchronize(ctx->stream), "sync drain_fit_domains");
-    const uint8_t* const h = ctx->dm_hout.p;
-    if (out_fits) std::memcpy(out_fits, h, (size_t)C);
-    if (out_moved) std::memcpy(out_moved, h + moved_at, (size_t)C * sizeof(int64_t));
-    if (out_fail_slot) std::memcpy(out_fail_slot, h + fail_at, (size_t)C * sizeof(int64_t));
-    if (out_target) std::memcpy(out_target, h + target_at, (size_t)S * sizeof(int32_t));
+    const uint8_t* const a = block_read_back(ctx, ans, "drain-fit", "sync drain_fit_domains");
+    block_part_to(out_fits, fits, a);
+    block_part_to(out_moved, moved, a);
+    block_part_to(out_fail_slot, fail, a);
+    block_part_to(out_target, target, a);
     ev.report_as("A=" + std::to_string(A) + " U=" + std::to_string(U) + " E=" + std::to_string(E));
     return PE_OK;
   });

@@ -56,38 +56,35 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
     const int64_t L0 = plan.n_leaf, ND = plan.n_dom;
     int64_t with_cand = 0;   // the jobs the rounds have to settle
     for (int64_t j = 0; j < J; ++j) with_cand += plan.cand_start[(size_t)j + 1] > plan.cand_start[(size_t)j];
-    // ---- one pinned block in: the groups, the jobs by index, the queues, then the plan's words
-    const size_t jobs_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t queue_at = jobs_at + (size_t)J * sizeof(pe::PlaceJob);
-    const size_t words_at = queue_at + (size_t)NP * sizeof(pe::FirstFitEntry);
-    const size_t in_bytes = words_at + (size_t)(L0 + ND + A + 1) * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned first-fit inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc first-fit inputs");
-    fill_place_groups((pe::PlaceGroup*)ctx->dm_hin.p, G, group_req, group_need, group_count, plan.pod_off.data());
-    pe::PlaceJob* const h_jobs = (pe::PlaceJob*)(ctx->dm_hin.p + jobs_at);
+    // ---- one pinned block in: the groups, the jobs by index, the queues, then the plan's words with q_start behind
+    pe::BlockLayout in;
+    const auto groups = in.add<pe::PlaceGroup>(G);
+    const auto jobs = in.add<pe::PlaceJob>(J);
+    const auto queue = in.add<pe::FirstFitEntry>(NP);
+    const auto words = in.add<int32_t>(L0 + ND + A + 1);
+    uint8_t* const h = block_in_host(ctx, in, "first-fit");
+    fill_place_groups(groups.in(h), G, group_req, group_need, group_count, plan.pod_off.data());
+    pe::PlaceJob* const h_jobs = jobs.in(h);
     for (int64_t j = 0; j < J; ++j) h_jobs[j] = pe::PlaceJob{(int32_t)j, job_group_off[j], job_group_off[j + 1], 0};
-    std::memcpy(ctx->dm_hin.p + queue_at, plan.queue.data(), (size_t)NP * sizeof(pe::FirstFitEntry));
-    int32_t* const h_q_start = pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), plan.leaf_dom, plan.act_of);
+    std::memcpy(queue.in(h), plan.queue.data(), queue.bytes());
+    int32_t* const h_q_start = pack_domain_words(words.in(h), plan.leaf_dom, plan.act_of);
     std::memcpy(h_q_start, plan.q_start.data(), (size_t)(A + 1) * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
-           "H2D first-fit inputs");
-    const pe::PlaceGroup* const d_groups = (const pe::PlaceGroup*)ctx->dm_in.p;
-    const pe::PlaceJob* const d_jobs = (const pe::PlaceJob*)(ctx->dm_in.p + jobs_at);
-    const pe::FirstFitEntry* const d_queue = (const pe::FirstFitEntry*)(ctx->dm_in.p + queue_at);
-    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
+    const uint8_t* const d = block_in_device(ctx, in, "first-fit");
+    const int32_t* const d_words = words.in(d);
     const int32_t* const d_q_start = d_words + L0 + ND;
     // ---- the call's device buffers; the answers: pods [P], pairs [J], statuses [J]
-    const size_t out_bytes = (size_t)(P + 2 * J) * sizeof(int32_t);
-    hipchk(ctx->dm_out.ensure(out_bytes), "alloc first-fit outputs");
-    hipchk(ctx->dm_hout.ensure(out_bytes), "alloc pinned first-fit outputs");
+    pe::BlockLayout ans;
+    const auto pods = ans.add<int32_t>(P, 4, true);
+    const auto pair = ans.add<int32_t>(J, 4, true);
+    const auto status = ans.add<int32_t>(J, 4, true);
+    uint8_t* const o = block_out_device(ctx, ans, "first-fit", true);
     hipchk(ctx->dm_log.ensure((size_t)(3 * P)), "alloc first-fit logs");
     hipchk(ctx->ff_state.ensure((size_t)(J + 1 + (A + 1) / 2)), "alloc first-fit state");
     hipchk(ctx->ff_hopen.ensure(1), "alloc pinned unsettled count");
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::FirstFitState state{ctx->ff_state.p, (int32_t*)(ctx->ff_state.p + J + 1), (uint32_t*)(ctx->ff_state.p + J)};
-    int32_t* const d_pods = (int32_t*)ctx->dm_out.p;
-    int32_t* const d_pair = d_pods + P;
-    int32_t* const d_status = d_pods + P + J;
+    int32_t* const d_pods = pods.in(o);
+    int32_t* const d_status = status.in(o);
     hipchk(hipMemsetAsync(state.word, 0, (size_t)(J + 1) * sizeof(uint64_t), ctx->stream), "zero first-fit state");
     hipchk(hipMemsetD32Async((hipDeviceptr_t)state.open, (int)with_cand, 1, ctx->stream), "set unsettled count");
     hipchk(hipMemcpyAsync(state.cursor, d_q_start, (size_t)A * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream),
@@ -117,8 +114,8 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
       const int64_t upto = std::min<int64_t>(rounds + per_read, max_rounds);
       per_read = std::min<int64_t>(2 * per_read, FF_ROUNDS_MAX);
       for (; rounds < upto; ++rounds)
-        hipchk(pe::launch_first_fit_round(ctx->stream, d_groups, d_jobs, d_q_start, d_queue, (int)A, segs, kinds,
-                                          (uint32_t)(rounds + 1), state, d_pods, d_status, d_pair, ctx->dm_log.p),
+        hipchk(pe::launch_first_fit_round(ctx->stream, groups.in(d), jobs.in(d), d_q_start, queue.in(d), (int)A, segs, kinds,
+                                          (uint32_t)(rounds + 1), state, d_pods, d_status, pair.in(o), ctx->dm_log.p),
                "launch first_fit_round");
       hipchk(hipMemcpyAsync(ctx->ff_hopen.p, state.open, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
              "D2H unsettled count");
@@ -128,16 +125,11 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
     hipchk(pe::launch_first_fit_finish(ctx->stream, segs, (int)A, ctx->Ns, ctx->res.p, ctx->stride, (uint64_t)ctx->begin),
            "launch first_fit_finish");
     ev.end();
-    hipchk(hipMemcpyAsync(ctx->dm_hout.p, ctx->dm_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream),
-           "D2H first-fit answers");
-    hipchk(hipStreamSynchronize(ctx->stream), "sync place_first_fit_domains");
-    const int32_t* const pods = (const int32_t*)ctx->dm_hout.p;
-    const int32_t* const pair = pods + P;
-    const int32_t* const status = pods + P + J;
-    if (P > 0) std::memcpy(out_pod_node, pods, (size_t)P * sizeof(int32_t));
-    std::memcpy(out_job_status, status, (size_t)J * sizeof(int32_t));
-    if (out_job_pair) std::memcpy(out_job_pair, pair, (size_t)J * sizeof(int32_t));
-    mirror_follow(ctx, "first_fit_round_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods, status);
+    const uint8_t* const a = block_read_back(ctx, ans, "first-fit", "sync place_first_fit_domains");
+    block_part_to(out_pod_node, pods, a);
+    block_part_to(out_job_status, status, a);
+    block_part_to(out_job_pair, pair, a);
+    mirror_follow(ctx, "first_fit_round_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods.in(a), status.in(a));
     ev.report_as("A=" + std::to_string(A) + " rounds=" + std::to_string(rounds));
     return PE_OK;
   });

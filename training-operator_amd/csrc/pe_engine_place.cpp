@@ -57,18 +57,18 @@ int place_in_domains(pe_ctx* ctx, const Entry& en, int64_t n_jobs, const int32_t
     const int64_t J = n_jobs, A = plan.n_active(), P = plan.pods();
     const int64_t L0 = plan.n_leaf, ND = plan.n_dom;
     // ---- one pinned block in: the groups, (min) their optional shares, the jobs in plan order, the plan's words
-    const size_t opt_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t jobs_at = opt_at + (min ? (size_t)G * sizeof(pe::PlaceMinOpt) : 0);
-    const size_t words_at = jobs_at + (size_t)J * (min ? sizeof(pe::PlaceMinJob) : sizeof(pe::PlaceJob));
-    const size_t in_bytes = words_at + (size_t)(L0 + ND + A + 1) * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned placement inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc placement inputs");
-    uint8_t* const h = ctx->dm_hin.p;
+    pe::BlockLayout in;
+    const auto groups = in.add<pe::PlaceGroup>(G);
+    const auto opt = in.add<pe::PlaceMinOpt>(min ? G : 0);
+    const auto jobs = in.add<pe::PlaceJob>(min ? 0 : J);
+    const auto mjobs = in.add<pe::PlaceMinJob>(min ? J : 0);
+    const auto words = in.add<int32_t>(L0 + ND + A + 1);
+    uint8_t* const h = block_in_host(ctx, in, "placement");
     if (min) {
-      fill_place_groups((pe::PlaceGroup*)h, G, group_req, group_need, mp.mand.data(), mp.mand_pod0.data());
-      pe::PlaceMinOpt* const h_opt = (pe::PlaceMinOpt*)(h + opt_at);
+      fill_place_groups(groups.in(h), G, group_req, group_need, mp.mand.data(), mp.mand_pod0.data());
+      pe::PlaceMinOpt* const h_opt = opt.in(h);
       for (int64_t g = 0; g < G; ++g) h_opt[g] = pe::PlaceMinOpt{mp.opt_pod0[(size_t)g], mp.opt[(size_t)g], 0};
-      pe::PlaceMinJob* const h_jobs = (pe::PlaceMinJob*)(h + jobs_at);
+      pe::PlaceMinJob* const h_jobs = mjobs.in(h);
       for (int64_t i = 0; i < J; ++i) {
         const int32_t j = plan.jobs[(size_t)i];
         h_jobs[i] = pe::PlaceMinJob{j,
@@ -79,51 +79,44 @@ int place_in_domains(pe_ctx* ctx, const Entry& en, int64_t n_jobs, const int32_t
                                     mp.job_pods[(size_t)j]};
       }
     } else {
-      fill_place_groups((pe::PlaceGroup*)h, G, group_req, group_need, group_count, plan.pod_off.data());
-      pe::PlaceJob* const h_jobs = (pe::PlaceJob*)(h + jobs_at);
+      fill_place_groups(groups.in(h), G, group_req, group_need, group_count, plan.pod_off.data());
+      pe::PlaceJob* const h_jobs = jobs.in(h);
       for (int64_t i = 0; i < J; ++i) {
         const int32_t j = plan.jobs[(size_t)i];
         h_jobs[i] = pe::PlaceJob{j, job_group_off[j], job_group_off[j + 1], 0};
       }
     }
-    int32_t* const h_start = pack_domain_words((int32_t*)(h + words_at), plan.leaf_dom, plan.act_of);
+    int32_t* const h_start = pack_domain_words(words.in(h), plan.leaf_dom, plan.act_of);
     std::memcpy(h_start, plan.job_start.data(), (size_t)(A + 1) * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, h, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D placement inputs");
-    const uint8_t* const d = ctx->dm_in.p;
-    const pe::PlaceGroup* const d_groups = (const pe::PlaceGroup*)d;
-    const int32_t* const d_words = (const int32_t*)(d + words_at);
+    const uint8_t* const d = block_in_device(ctx, in, "placement");
+    const int32_t* const d_words = words.in(d);
     // ---- the call's device buffers: one block out -- pods [P], statuses [J], (min) the groups' placed pods [G]
-    const int64_t n_out = P + J + (min ? G : 0);
-    hipchk(ctx->dm_out.ensure((size_t)n_out * sizeof(int32_t)), "alloc placement outputs");
-    hipchk(ctx->dm_hout.ensure((size_t)n_out * sizeof(int32_t)), "alloc pinned placement outputs");
+    pe::BlockLayout ans;
+    const auto pods = ans.add<int32_t>(P, 4, true);
+    const auto status = ans.add<int32_t>(J, 4, true);
+    const auto gpods = ans.add<int32_t>(min ? G : 0, 4, true);
+    uint8_t* const o = block_out_device(ctx, ans, "placement", true);
     hipchk(ctx->dm_log.ensure((size_t)(3 * (min ? mp.mand_pods : P))), "alloc placement logs");
-    int32_t* const d_out = (int32_t*)ctx->dm_out.p;
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     if (min && G > 0)   // a failed job's groups hold no pod: the kernel leaves them as they are
-      hipchk(hipMemsetAsync(d_out + P + J, 0, (size_t)G * sizeof(int32_t), ctx->stream), "zero group pods");
+      hipchk(hipMemsetAsync(gpods.in(o), 0, gpods.bytes(), ctx->stream), "zero group pods");
     CapEvents ev(ctx);
     ev.begin();
     launch_domain_members(ctx, d_words, L0, A, segs);
-    hipchk(min ? pe::launch_place_min_domains(ctx->stream, d_groups, (const pe::PlaceMinOpt*)(d + opt_at),
-                                              (const pe::PlaceMinJob*)(d + jobs_at), d_words + L0 + ND, (int)A, segs,
-                                              ctx->res.p, ctx->stride, (uint64_t)ctx->begin, d_out, d_out + P,
-                                              d_out + P + J, ctx->dm_log.p)
-               : pe::launch_place_domains(ctx->stream, d_groups, (const pe::PlaceJob*)(d + jobs_at), d_words + L0 + ND,
-                                          (int)A, segs, ctx->res.p, ctx->stride, (uint64_t)ctx->begin, d_out, d_out + P,
+    hipchk(min ? pe::launch_place_min_domains(ctx->stream, groups.in(d), opt.in(d), mjobs.in(d), d_words + L0 + ND, (int)A,
+                                              segs, ctx->res.p, ctx->stride, (uint64_t)ctx->begin, pods.in(o),
+                                              status.in(o), gpods.in(o), ctx->dm_log.p)
+               : pe::launch_place_domains(ctx->stream, groups.in(d), jobs.in(d), d_words + L0 + ND, (int)A, segs,
+                                          ctx->res.p, ctx->stride, (uint64_t)ctx->begin, pods.in(o), status.in(o),
                                           ctx->dm_log.p),
            en.launch);
     ev.end();
-    hipchk(hipMemcpyAsync(ctx->dm_hout.p, d_out, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream),
-           "D2H placements");
-    hipchk(hipStreamSynchronize(ctx->stream), en.sync);
-    const int32_t* const pods = (const int32_t*)ctx->dm_hout.p;
-    const int32_t* const status = pods + P;
-    const int32_t* const gpods = min ? pods + P + J : nullptr;
-    if (P > 0) std::memcpy(out_pod_node, pods, (size_t)P * sizeof(int32_t));
-    std::memcpy(out_job_status, status, (size_t)J * sizeof(int32_t));
-    if (min && out_group_pods && G > 0) std::memcpy(out_group_pods, gpods, (size_t)G * sizeof(int32_t));
-    mirror_follow(ctx, en.kernel, J, job_group_off, group_req, plan.pod_off.data(), pods, status, gpods,
-                  min ? out_job_pods : nullptr);
+    const uint8_t* const a = block_read_back(ctx, ans, "placement", en.sync, "D2H placements");
+    block_part_to(out_pod_node, pods, a);
+    block_part_to(out_job_status, status, a);
+    block_part_to(out_group_pods, gpods, a);
+    mirror_follow(ctx, en.kernel, J, job_group_off, group_req, plan.pod_off.data(), pods.in(a), status.in(a),
+                  min ? gpods.in(a) : nullptr, min ? out_job_pods : nullptr);
     ev.report_as("A=" + std::to_string(A));
     return PE_OK;
   });

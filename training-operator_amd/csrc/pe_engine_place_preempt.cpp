@@ -80,58 +80,54 @@ int pe_place_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_gro
     const pe::PlacePlan& plan = pp.base;
     const int64_t A = plan.n_active(), P = plan.pods(), L0 = plan.n_leaf, ND = plan.n_dom, R = pp.n_recs();
     const int64_t NL = job_vic_off[J];
-    // ---- one pinned block in: the groups, the records (8-B aligned so far), the jobs in plan order, then the record
-    // CSR, the victims' active domains, the lists and the plan's words with job_start behind them
-    const size_t recs_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t jobs_at = recs_at + (size_t)R * sizeof(pe::PreRec);
-    const size_t rstart_at = jobs_at + (size_t)J * sizeof(pe::PreemptJob);
-    const size_t act_at = rstart_at + (size_t)(V + 1) * sizeof(int32_t);
-    const size_t list_at = act_at + (size_t)V * sizeof(int32_t);
-    const size_t words_at = list_at + (size_t)NL * sizeof(int32_t);
-    const size_t in_bytes = words_at + (size_t)(L0 + ND + A + 1) * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned place-preempt inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc place-preempt inputs");
-    uint8_t* const h = ctx->dm_hin.p;
-    fill_place_groups((pe::PlaceGroup*)h, G, group_req, group_need, group_count, plan.pod_off.data());
-    if (R > 0) std::memcpy(h + recs_at, pp.recs.data(), (size_t)R * sizeof(pe::PreRec));
-    std::memcpy(h + jobs_at, pp.jobs.data(), (size_t)J * sizeof(pe::PreemptJob));
-    std::memcpy(h + rstart_at, pp.rec_start.data(), (size_t)(V + 1) * sizeof(int32_t));
-    if (V > 0) std::memcpy(h + act_at, pp.vic_act.data(), (size_t)V * sizeof(int32_t));
-    if (NL > 0) std::memcpy(h + list_at, job_vic, (size_t)NL * sizeof(int32_t));
-    int32_t* const h_start = pack_domain_words((int32_t*)(h + words_at), plan.leaf_dom, plan.act_of);
+    // ---- one pinned block in: the groups, the records, the jobs in plan order, then the record CSR, the victims'
+    // active domains, the lists and the plan's words with job_start behind them
+    pe::BlockLayout bl;
+    const auto groups = bl.add<pe::PlaceGroup>(G);
+    const auto recs = bl.add<pe::PreRec>(R);
+    const auto jobs = bl.add<pe::PreemptJob>(J);
+    const auto rstart = bl.add<int32_t>(V + 1);
+    const auto act = bl.add<int32_t>(V);
+    const auto list = bl.add<int32_t>(NL);
+    const auto words = bl.add<int32_t>(L0 + ND + A + 1);
+    uint8_t* const h = block_in_host(ctx, bl, "place-preempt");
+    fill_place_groups(groups.in(h), G, group_req, group_need, group_count, plan.pod_off.data());
+    if (R > 0) std::memcpy(recs.in(h), pp.recs.data(), recs.bytes());
+    std::memcpy(jobs.in(h), pp.jobs.data(), jobs.bytes());
+    std::memcpy(rstart.in(h), pp.rec_start.data(), rstart.bytes());
+    if (V > 0) std::memcpy(act.in(h), pp.vic_act.data(), act.bytes());
+    if (NL > 0) std::memcpy(list.in(h), job_vic, list.bytes());
+    int32_t* const h_start = pack_domain_words(words.in(h), plan.leaf_dom, plan.act_of);
     std::memcpy(h_start, plan.job_start.data(), (size_t)(A + 1) * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, h, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D place-preempt inputs");
-    const uint8_t* const d = ctx->dm_in.p;
-    const int32_t* const d_words = (const int32_t*)(d + words_at);
+    const uint8_t* const d = block_in_device(ctx, bl, "place-preempt");
+    const int32_t* const d_words = words.in(d);
     // ---- one block out: the masks [J] and the attempt counter (64-bit cells), then pods [P], statuses and prefixes
     // [J] and the evicting jobs [V]
-    const size_t tries_at = (size_t)J * sizeof(uint64_t);
-    const size_t pods_at = tries_at + sizeof(uint64_t);
-    const size_t status_at = pods_at + (size_t)P * sizeof(int32_t);
-    const size_t prefix_at = status_at + (size_t)J * sizeof(int32_t);
-    const size_t vjob_at = prefix_at + (size_t)J * sizeof(int32_t);
-    const size_t out_bytes = vjob_at + (size_t)V * sizeof(int32_t);
-    hipchk(ctx->dm_out.ensure(out_bytes), "alloc place-preempt outputs");
-    hipchk(ctx->dm_hout.ensure(out_bytes), "alloc pinned place-preempt outputs");
+    pe::BlockLayout ans;
+    const auto masks = ans.add<uint64_t>(J, 8, true);
+    const auto tries = ans.add<unsigned long long>(1, 8, true);
+    const auto pods = ans.add<int32_t>(P, 4, true);
+    const auto status = ans.add<int32_t>(J, 4, true);
+    const auto prefix = ans.add<int32_t>(J, 4, true);
+    const auto vjob = ans.add<int32_t>(V, 4, true);
+    uint8_t* const o = block_out_device(ctx, ans, "place-preempt", true);
     hipchk(ctx->dm_log.ensure((size_t)(3 * P)), "alloc placement logs");
     hipchk(ctx->pp_place.ensure((size_t)std::max<int64_t>(ctx->Ns, 1)), "alloc node places");
-    uint8_t* const o = ctx->dm_out.p;
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::PlacePreIn in{};
-    in.groups = (const pe::PlaceGroup*)d;
-    in.jobs = (const pe::PreemptJob*)(d + jobs_at);
+    in.groups = groups.in(d);
+    in.jobs = jobs.in(d);
     in.job_start = d_words + L0 + ND;
-    in.list = (const int32_t*)(d + list_at);
-    in.rec_start = (const int32_t*)(d + rstart_at);
-    in.recs = (const pe::PreRec*)(d + recs_at);
-    in.vic_act = (const int32_t*)(d + act_at);
+    in.list = list.in(d);
+    in.rec_start = rstart.in(d);
+    in.recs = recs.in(d);
+    in.vic_act = act.in(d);
     in.node_place = ctx->pp_place.p;
     in.Ns = ctx->Ns;
     in.id_base = (uint64_t)ctx->begin;
-    const pe::PlacePreOut out{(int32_t*)(o + pods_at),   (int32_t*)(o + status_at), (int32_t*)(o + prefix_at),
-                              (uint64_t*)o,              (int32_t*)(o + vjob_at),   (unsigned long long*)(o + tries_at)};
-    hipchk(hipMemsetAsync(out.attempts, 0, sizeof(uint64_t), ctx->stream), "zero the attempt counter");
-    if (V > 0) hipchk(hipMemsetAsync(out.vic_job, 0xFF, (size_t)V * sizeof(int32_t), ctx->stream), "clear evicting jobs");
+    const pe::PlacePreOut out{pods.in(o), status.in(o), prefix.in(o), masks.in(o), vjob.in(o), tries.in(o)};
+    hipchk(hipMemsetAsync(out.attempts, 0, tries.bytes(), ctx->stream), "zero the attempt counter");
+    if (V > 0) hipchk(hipMemsetAsync(out.vic_job, 0xFF, vjob.bytes(), ctx->stream), "clear evicting jobs");
     if (ctx->Ns > 0)
       hipchk(hipMemsetAsync(ctx->pp_place.p, 0xFF, (size_t)ctx->Ns * sizeof(int32_t), ctx->stream), "clear node places");
     CapEvents ev(ctx);
@@ -145,21 +141,17 @@ int pe_place_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_gro
       hipchk(pe::launch_place_preempt_sweep(ctx->stream, in, V, segs, out.vic_job, ctx->res.p, ctx->stride),
              "launch place_preempt_sweep");
     ev.end();
-    hipchk(hipMemcpyAsync(ctx->dm_hout.p, o, out_bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H place-preempt answers");
-    hipchk(hipStreamSynchronize(ctx->stream), "sync place_preempt_domains");
-    const uint8_t* const a = ctx->dm_hout.p;
-    const int32_t* const pods = (const int32_t*)(a + pods_at);
-    const int32_t* const status = (const int32_t*)(a + status_at);
-    const int32_t* const vjob = (const int32_t*)(a + vjob_at);
-    if (P > 0) std::memcpy(out_pod_node, pods, (size_t)P * sizeof(int32_t));
-    std::memcpy(out_job_status, status, (size_t)J * sizeof(int32_t));
-    if (out_job_prefix) std::memcpy(out_job_prefix, a + prefix_at, (size_t)J * sizeof(int32_t));
-    if (out_job_victims) std::memcpy(out_job_victims, a, (size_t)J * sizeof(uint64_t));
-    if (out_vic_job && V > 0) std::memcpy(out_vic_job, vjob, (size_t)V * sizeof(int32_t));
+    const uint8_t* const a = block_read_back(ctx, ans, "place-preempt", "sync place_preempt_domains");
+    block_part_to(out_pod_node, pods, a);
+    block_part_to(out_job_status, status, a);
+    block_part_to(out_job_prefix, prefix, a);
+    block_part_to(out_job_victims, masks, a);
+    block_part_to(out_vic_job, vjob, a);
+    const int32_t* const evictor = vjob.in(a);
     int64_t evicted = 0;
     for (int64_t v = 0; v < V; ++v) {
-      if (vjob[v] < 0) continue;
-      if (vjob[v] >= J || pp.vic_act[(size_t)v] < 0) raise(PE_EHIP, "place_preempt_kernel: a victim evicted by no job");
+      if (evictor[v] < 0) continue;
+      if (evictor[v] >= J || pp.vic_act[(size_t)v] < 0) raise(PE_EHIP, "place_preempt_kernel: a victim evicted by no job");
       ++evicted;
       if (pp.dry_run) continue;
       for (int32_t r = pp.rec_start[(size_t)v]; r < pp.rec_start[(size_t)v + 1]; ++r) {   // the gang leaves whole
@@ -170,12 +162,11 @@ int pe_place_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_gro
       }
     }
     if (!pp.dry_run)
-      mirror_follow(ctx, "place_preempt_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods, status);
-    if (ev.on) {
-      uint64_t tries = 0;
-      std::memcpy(&tries, a + tries_at, sizeof(tries));
-      ev.report_as("A=" + std::to_string(A) + " attempts=" + std::to_string(tries) + " evicted=" + std::to_string(evicted));
-    }
+      mirror_follow(ctx, "place_preempt_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods.in(a),
+                    status.in(a));
+    if (ev.on)
+      ev.report_as("A=" + std::to_string(A) + " attempts=" + std::to_string(*tries.in(a)) +
+                   " evicted=" + std::to_string(evicted));
     return PE_OK;
   });
 }

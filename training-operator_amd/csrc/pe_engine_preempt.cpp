@@ -75,62 +75,59 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
       return PE_OK;
     }
     const int64_t L0 = fit.n_leaf, ND = fit.n_dom, R = plan.n_recs(), NL = (int64_t)plan.list.size();
-    // ---- one pinned block in: the groups, the pairs in plan order, the units, the records (8-B aligned so far),
-    // then the record CSR, the lists and the plan's words
-    const size_t pairs_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t units_at = pairs_at + (size_t)P * sizeof(pe::PrePair);
-    const size_t recs_at = units_at + (size_t)U * sizeof(pe::FitUnit);
-    const size_t rstart_at = recs_at + (size_t)R * sizeof(pe::PreRec);
-    const size_t list_at = rstart_at + (size_t)(V + 1) * sizeof(int32_t);
-    const size_t words_at = list_at + (size_t)NL * sizeof(int32_t);
-    const size_t in_bytes = words_at + (size_t)(L0 + ND) * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned gang-preempt inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc gang-preempt inputs");
-    fill_place_groups((pe::PlaceGroup*)ctx->dm_hin.p, G, group_req, group_need, group_count, nullptr);
-    pe::PrePair* const h_pairs = (pe::PrePair*)(ctx->dm_hin.p + pairs_at);
+    // ---- one pinned block in: the groups, the pairs in plan order, the units, the records, then the record CSR,
+    // the lists and the plan's words
+    pe::BlockLayout bl;
+    const auto groups = bl.add<pe::PlaceGroup>(G);
+    const auto pairs = bl.add<pe::PrePair>(P);
+    const auto units = bl.add<pe::FitUnit>(U);
+    const auto recs = bl.add<pe::PreRec>(R);
+    const auto rstart = bl.add<int32_t>(V + 1);
+    const auto list = bl.add<int32_t>(NL);
+    const auto words = bl.add<int32_t>(L0 + ND);
+    uint8_t* const h = block_in_host(ctx, bl, "gang-preempt");
+    fill_place_groups(groups.in(h), G, group_req, group_need, group_count, nullptr);
+    pe::PrePair* const h_pairs = pairs.in(h);
     for (int64_t i = 0; i < P; ++i) {
       const int32_t p = fit.pairs[(size_t)i], j = pair_job[p];
       h_pairs[i] = pe::PrePair{p, j, job_group_off[j], job_group_off[j + 1], plan.list_start[(size_t)i],
                                plan.list_start[(size_t)i + 1], {0, 0}};
     }
-    std::memcpy(ctx->dm_hin.p + units_at, fit.units.data(), (size_t)U * sizeof(pe::FitUnit));
-    std::memcpy(ctx->dm_hin.p + recs_at, plan.recs.data(), (size_t)R * sizeof(pe::PreRec));
-    std::memcpy(ctx->dm_hin.p + rstart_at, plan.rec_start.data(), (size_t)(V + 1) * sizeof(int32_t));
-    std::memcpy(ctx->dm_hin.p + list_at, plan.list.data(), (size_t)NL * sizeof(int32_t));
-    pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), fit.leaf_dom, fit.act_of);
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream),
-           "H2D gang-preempt inputs");
-    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
-    // ---- the call's device buffers; the answers: best [J] and the judgement counter (64-bit cells), then victims,
-    // prefix and count [P], 16-B aligned
-    const size_t judged_at = (size_t)J * sizeof(uint64_t);
-    const size_t vict_at = r16(judged_at + sizeof(uint64_t));
-    const size_t prefix_at = vict_at + r16((size_t)P * sizeof(uint64_t));
-    const size_t count_at = prefix_at + r16((size_t)P * sizeof(int32_t));
-    const size_t out_bytes = count_at + (size_t)P * sizeof(int32_t);
-    hipchk(ctx->dm_out.ensure(out_bytes), "alloc gang-preempt outputs");
+    std::memcpy(units.in(h), fit.units.data(), units.bytes());
+    std::memcpy(recs.in(h), plan.recs.data(), recs.bytes());
+    std::memcpy(rstart.in(h), plan.rec_start.data(), rstart.bytes());
+    std::memcpy(list.in(h), plan.list.data(), list.bytes());
+    pack_domain_words(words.in(h), fit.leaf_dom, fit.act_of);
+    const uint8_t* const d = block_in_device(ctx, bl, "gang-preempt");
+    // ---- the call's device buffers; the answers: best [J] and the judgement counter (64-bit cells; it crosses with
+    // best, or alone for the diagnostics), then victims, prefix and count [P], 16-B aligned
+    CapEvents ev(ctx);
+    pe::BlockLayout ans;
+    const auto best = ans.add<unsigned long long>(J, 16, out_best != nullptr);
+    const auto judged = ans.add<unsigned long long>(1, 8, out_best || ev.on);
+    const auto victims = ans.add<uint64_t>(P, 16, out_victims != nullptr);
+    const auto prefix = ans.add<int32_t>(P, 16, out_prefix != nullptr);
+    const auto count = ans.add<int32_t>(P, 16, out_count != nullptr);
+    uint8_t* const o = block_out_device(ctx, ans, "gang-preempt");
     hipchk(ctx->pp_place.ensure((size_t)std::max<int64_t>(ctx->Ns, 1)), "alloc node places");
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::PreIn in{};
-    in.groups = (const pe::PlaceGroup*)ctx->dm_in.p;
-    in.pairs = (const pe::PrePair*)(ctx->dm_in.p + pairs_at);
-    in.units = (const pe::FitUnit*)(ctx->dm_in.p + units_at);
-    in.recs = (const pe::PreRec*)(ctx->dm_in.p + recs_at);
-    in.rec_start = (const int32_t*)(ctx->dm_in.p + rstart_at);
-    in.list = (const int32_t*)(ctx->dm_in.p + list_at);
+    in.groups = groups.in(d);
+    in.pairs = pairs.in(d);
+    in.units = units.in(d);
+    in.recs = recs.in(d);
+    in.rec_start = rstart.in(d);
+    in.list = list.in(d);
     in.node_place = ctx->pp_place.p;
     in.Ns = ctx->Ns;
     in.id_base = (uint64_t)ctx->begin;
-    pe::PreOut out{(unsigned long long*)ctx->dm_out.p, (unsigned long long*)(ctx->dm_out.p + judged_at),
-                   (uint64_t*)(ctx->dm_out.p + vict_at), (int32_t*)(ctx->dm_out.p + prefix_at),
-                   (int32_t*)(ctx->dm_out.p + count_at)};
-    hipchk(hipMemsetAsync(out.best, 0xFF, judged_at, ctx->stream), "clear best pairs");
-    hipchk(hipMemsetAsync(out.judged, 0, sizeof(uint64_t), ctx->stream), "zero the judgement counter");
+    pe::PreOut out{best.in(o), judged.in(o), victims.in(o), prefix.in(o), count.in(o)};
+    hipchk(hipMemsetAsync(out.best, 0xFF, best.bytes(), ctx->stream), "clear best pairs");
+    hipchk(hipMemsetAsync(out.judged, 0, judged.bytes(), ctx->stream), "zero the judgement counter");
     if (ctx->Ns > 0)
       hipchk(hipMemsetAsync(ctx->pp_place.p, 0xFF, (size_t)ctx->Ns * sizeof(int32_t), ctx->stream), "clear node places");
-    CapEvents ev(ctx);
     ev.begin();
-    launch_domain_members(ctx, d_words, L0, A, segs);
+    launch_domain_members(ctx, words.in(d), L0, A, segs);
     hipchk(pe::launch_preempt_place_map(ctx->stream, segs, (int)A, ctx->Ns, (uint64_t)ctx->begin, ctx->pp_place.p),
            "launch preempt_place_map");
     const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
@@ -140,32 +137,14 @@ int pe_gang_preempt_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
         ctx, segs, A, fit, [&]() { launch(U, {}, "launch preempt_domains (LDS)"); },
         [&](const LargeSegs& large) { launch(large.n, large, "launch preempt_domains (global)"); });
     ev.end();
-    // ---- one copy out: the span from the first to the last answer the caller asked for (the judgement counter
-    // lies behind best and crosses with it, or alone for the diagnostics)
-    const size_t lo = out_best ? 0 : ev.on ? judged_at : out_victims ? vict_at : out_prefix ? prefix_at : count_at;
-    const size_t hi = out_count     ? out_bytes
-                      : out_prefix  ? prefix_at + (size_t)P * sizeof(int32_t)
-                      : out_victims ? vict_at + (size_t)P * sizeof(uint64_t)
-                                    : judged_at + sizeof(uint64_t);
-    if (out_best || out_victims || out_prefix || out_count || ev.on) {
-      hipchk(ctx->dm_hout.ensure(hi), "alloc pinned gang-preempt outputs");
-      hipchk(hipMemcpyAsync(ctx->dm_hout.p + lo, ctx->dm_out.p + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream),
-             "D2H gang-preempt answers");
-    }
-    hipchk(hipStreamSynchronize(ctx->stream), "sync gang_preempt_domains");
-    const uint8_t* const h = ctx->dm_hout.p;
-    if (out_best) {   // the low half of the minimum is the pair; ~0 reads as -1: no pair has an answer
-      const uint64_t* const best = (const uint64_t*)h;
-      for (int64_t j = 0; j < J; ++j) out_best[j] = (int32_t)(uint32_t)best[j];
-    }
-    if (out_victims) std::memcpy(out_victims, h + vict_at, (size_t)P * sizeof(uint64_t));
-    if (out_prefix) std::memcpy(out_prefix, h + prefix_at, (size_t)P * sizeof(int32_t));
-    if (out_count) std::memcpy(out_count, h + count_at, (size_t)P * sizeof(int32_t));
-    if (ev.on) {
-      uint64_t judged = 0;
-      std::memcpy(&judged, h + judged_at, sizeof(judged));
-      ev.report_as("A=" + std::to_string(A) + " U=" + std::to_string(U) + " judged=" + std::to_string(judged));
-    }
+    // ---- one copy out: the span from the first to the last answer the caller asked for
+    const uint8_t* const a = block_read_back(ctx, ans, "gang-preempt", "sync gang_preempt_domains");
+    block_best_to(out_best, best, a);
+    block_part_to(out_victims, victims, a);
+    block_part_to(out_prefix, prefix, a);
+    block_part_to(out_count, count, a);
+    if (ev.on)
+      ev.report_as("A=" + std::to_string(A) + " U=" + std::to_string(U) + " judged=" + std::to_string(*judged.in(a)));
     return PE_OK;
   });
 }

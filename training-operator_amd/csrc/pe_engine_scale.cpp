@@ -62,58 +62,56 @@ int pe_scale_up_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_of
       return PE_OK;
     }
     const int64_t L0 = fit.n_leaf, ND = fit.n_dom;
-    // ---- one pinned block in: the groups, the pairs in plan order, the templates' residuals (8-B aligned so far),
-    // the units, then the templates' labels, the new slots and the plan's words
-    const size_t pairs_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t tres_at = pairs_at + (size_t)P * sizeof(pe::ScalePair);
-    const size_t units_at = tres_at + (size_t)T * pe::D * sizeof(int64_t);
-    const size_t tlab_at = units_at + (size_t)U * sizeof(pe::FitUnit);
-    const size_t slots_at = tlab_at + (size_t)T * sizeof(uint32_t);
-    const size_t words_at = slots_at + (size_t)n_new * sizeof(int32_t);
-    const size_t in_bytes = words_at + (size_t)(L0 + ND) * sizeof(int32_t);
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned scale-up inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc scale-up inputs");
-    fill_place_groups((pe::PlaceGroup*)ctx->dm_hin.p, G, group_req, group_need, group_count, nullptr);
-    pe::ScalePair* const h_pairs = (pe::ScalePair*)(ctx->dm_hin.p + pairs_at);
+    // ---- one pinned block in: the groups, the pairs in plan order, the templates' residuals, the units, then the
+    // templates' labels, the new slots and the plan's words
+    pe::BlockLayout bl;
+    const auto groups = bl.add<pe::PlaceGroup>(G);
+    const auto pairs = bl.add<pe::ScalePair>(P);
+    const auto tres = bl.add<int64_t>(T * pe::D);
+    const auto units = bl.add<pe::FitUnit>(U);
+    const auto tlab = bl.add<uint32_t>(T);
+    const auto slots = bl.add<int32_t>(n_new);
+    const auto words = bl.add<int32_t>(L0 + ND);
+    uint8_t* const h = block_in_host(ctx, bl, "scale-up");
+    fill_place_groups(groups.in(h), G, group_req, group_need, group_count, nullptr);
+    pe::ScalePair* const h_pairs = pairs.in(h);
     int64_t attempts = 0;   // the judgements the call may cost
     for (int64_t i = 0; i < P; ++i) {
       const int32_t p = fit.pairs[(size_t)i], j = pair_job[p];
       h_pairs[i] = pe::ScalePair{p, j, job_group_off[j], job_group_off[j + 1], pair_template[p], plan.kmax[(size_t)i], {0, 0}};
       attempts += plan.kmax[(size_t)i] + 1;
     }
-    std::memcpy(ctx->dm_hin.p + tres_at, tmpl_res, (size_t)T * pe::D * sizeof(int64_t));
-    std::memcpy(ctx->dm_hin.p + units_at, fit.units.data(), (size_t)U * sizeof(pe::FitUnit));
-    uint32_t* const h_tlab = (uint32_t*)(ctx->dm_hin.p + tlab_at);
+    std::memcpy(tres.in(h), tmpl_res, tres.bytes());
+    std::memcpy(units.in(h), fit.units.data(), units.bytes());
+    uint32_t* const h_tlab = tlab.in(h);
     for (int64_t t = 0; t < T; ++t)   // a node in a domain has an island: the caller's bit 31 is replaced
       h_tlab[t] = (tmpl_labels ? tmpl_labels[t] : 0u) | PE_LABEL_ISLAND;
-    if (n_new > 0) std::memcpy(ctx->dm_hin.p + slots_at, new_slot, (size_t)n_new * sizeof(int32_t));
-    pack_domain_words((int32_t*)(ctx->dm_hin.p + words_at), fit.leaf_dom, fit.act_of);
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, ctx->dm_hin.p, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D scale-up inputs");
-    const int32_t* const d_words = (const int32_t*)(ctx->dm_in.p + words_at);
+    if (n_new > 0) std::memcpy(slots.in(h), new_slot, slots.bytes());
+    pack_domain_words(words.in(h), fit.leaf_dom, fit.act_of);
+    const uint8_t* const d = block_in_device(ctx, bl, "scale-up");
     // ---- the call's device buffers; the answers: best [J] (64-bit cells), then nodes, fail_group, pods and new_pods
     // [P], 16-B aligned
-    const size_t nodes_at = r16((size_t)J * sizeof(uint64_t));
-    const size_t fail_at = nodes_at + r16((size_t)P * sizeof(int32_t));
-    const size_t pods_at = fail_at + r16((size_t)P * sizeof(int32_t));
-    const size_t newp_at = pods_at + r16((size_t)P * sizeof(int64_t));
-    const size_t out_bytes = newp_at + (size_t)P * sizeof(int64_t);
-    hipchk(ctx->dm_out.ensure(out_bytes), "alloc scale-up outputs");
+    pe::BlockLayout ans;
+    const auto best = ans.add<unsigned long long>(J, 16, out_best != nullptr);
+    const auto nodes = ans.add<int32_t>(P, 16, out_nodes != nullptr);
+    const auto fail = ans.add<int32_t>(P, 16, out_fail_group != nullptr);
+    const auto pods = ans.add<int64_t>(P, 16, out_pods != nullptr);
+    const auto newp = ans.add<int64_t>(P, 16, out_new_pods != nullptr);
+    uint8_t* const o = block_out_device(ctx, ans, "scale-up");
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     pe::ScaleIn in{};
-    in.groups = (const pe::PlaceGroup*)ctx->dm_in.p;
-    in.pairs = (const pe::ScalePair*)(ctx->dm_in.p + pairs_at);
-    in.units = (const pe::FitUnit*)(ctx->dm_in.p + units_at);
-    in.tmpl_res = (const int64_t*)(ctx->dm_in.p + tres_at);
-    in.tmpl_lab = (const uint32_t*)(ctx->dm_in.p + tlab_at);
-    in.new_slot = (const int32_t*)(ctx->dm_in.p + slots_at);
+    in.groups = groups.in(d);
+    in.pairs = pairs.in(d);
+    in.units = units.in(d);
+    in.tmpl_res = tres.in(d);
+    in.tmpl_lab = tlab.in(d);
+    in.new_slot = slots.in(d);
     in.n_new = n_new;
-    pe::ScaleOut out{(unsigned long long*)ctx->dm_out.p, (int32_t*)(ctx->dm_out.p + nodes_at),
-                     (int32_t*)(ctx->dm_out.p + fail_at), (int64_t*)(ctx->dm_out.p + pods_at),
-                     (int64_t*)(ctx->dm_out.p + newp_at)};
-    hipchk(hipMemsetAsync(out.best, 0xFF, (size_t)J * sizeof(uint64_t), ctx->stream), "clear best pairs");
+    pe::ScaleOut out{best.in(o), nodes.in(o), fail.in(o), pods.in(o), newp.in(o)};
+    hipchk(hipMemsetAsync(out.best, 0xFF, best.bytes(), ctx->stream), "clear best pairs");
     CapEvents ev(ctx);
     ev.begin();
-    launch_domain_members(ctx, d_words, L0, A, segs);
+    launch_domain_members(ctx, words.in(d), L0, A, segs);
     const auto launch = [&](int64_t blocks, const LargeSegs& large, const char* what) {
       hipchk(pe::launch_scale(ctx->stream, in, blocks, large.recs, large.scratch, segs, out), what);
     };
@@ -122,27 +120,12 @@ int pe_scale_up_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_of
         [&](const LargeSegs& large) { launch(large.n, large, "launch scale_domains (global)"); });
     ev.end();
     // ---- one copy out: the span from the first to the last answer the caller asked for
-    const size_t lo = out_best ? 0 : out_nodes ? nodes_at : out_fail_group ? fail_at : out_pods ? pods_at : newp_at;
-    const size_t hi = out_new_pods     ? out_bytes
-                      : out_pods       ? pods_at + (size_t)P * sizeof(int64_t)
-                      : out_fail_group ? fail_at + (size_t)P * sizeof(int32_t)
-                      : out_nodes      ? nodes_at + (size_t)P * sizeof(int32_t)
-                                       : (size_t)J * sizeof(uint64_t);
-    if (out_best || out_nodes || out_fail_group || out_pods || out_new_pods) {
-      hipchk(ctx->dm_hout.ensure(hi), "alloc pinned scale-up outputs");
-      hipchk(hipMemcpyAsync(ctx->dm_hout.p + lo, ctx->dm_out.p + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream),
-             "D2H scale-up answers");
-    }
-    hipchk(hipStreamSynchronize(ctx->stream), "sync scale_up_domains");
-    const uint8_t* const h = ctx->dm_hout.p;
-    if (out_best) {   // the low half of the minimum is the pair; ~0 reads as -1: no pair has an answer
-      const uint64_t* const best = (const uint64_t*)h;
-      for (int64_t j = 0; j < J; ++j) out_best[j] = (int32_t)(uint32_t)best[j];
-    }
-    if (out_nodes) std::memcpy(out_nodes, h + nodes_at, (size_t)P * sizeof(int32_t));
-    if (out_fail_group) std::memcpy(out_fail_group, h + fail_at, (size_t)P * sizeof(int32_t));
-    if (out_pods) std::memcpy(out_pods, h + pods_at, (size_t)P * sizeof(int64_t));
-    if (out_new_pods) std::memcpy(out_new_pods, h + newp_at, (size_t)P * sizeof(int64_t));
+    const uint8_t* const a = block_read_back(ctx, ans, "scale-up", "sync scale_up_domains");
+    block_best_to(out_best, best, a);
+    block_part_to(out_nodes, nodes, a);
+    block_part_to(out_fail_group, fail, a);
+    block_part_to(out_pods, pods, a);
+    block_part_to(out_new_pods, newp, a);
     ev.report_as("A=" + std::to_string(A) + " U=" + std::to_string(U) + " attempts<=" + std::to_string(attempts));
     return PE_OK;
   });

@@ -39,34 +39,32 @@ int pe_place_spread_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
     const bool by_node = sp.by_node();
     const int64_t J = n_jobs, A = plan.n_active(), P = plan.pods();
     const int64_t L0 = plan.n_leaf, ND = plan.n_dom;
-    // ---- one pinned block in: the groups, their caps, the jobs in plan order, the plan's words, leaf_sub
-    const size_t caps_at = (size_t)G * sizeof(pe::PlaceGroup);
-    const size_t jobs_at = r16(caps_at + (size_t)G * sizeof(int32_t));
-    const size_t words_at = jobs_at + (size_t)J * sizeof(pe::PlaceJob);
-    const size_t sub_at = words_at + (size_t)(L0 + ND + A + 1) * sizeof(int32_t);
-    const size_t in_bytes = sub_at + (by_node ? 0 : (size_t)L0 * sizeof(int32_t));
-    hipchk(ctx->dm_hin.ensure(in_bytes), "alloc pinned placement inputs");
-    hipchk(ctx->dm_in.ensure(in_bytes), "alloc placement inputs");
-    uint8_t* const h = ctx->dm_hin.p;
-    fill_place_groups((pe::PlaceGroup*)h, G, group_req, group_need, group_count, plan.pod_off.data());
-    if (G > 0) std::memcpy(h + caps_at, sp.cap.data(), (size_t)G * sizeof(int32_t));
-    pe::PlaceJob* const h_jobs = (pe::PlaceJob*)(h + jobs_at);
+    // ---- one pinned block in: the groups, their caps, the jobs in plan order (16-B aligned), the plan's words, leaf_sub
+    pe::BlockLayout in;
+    const auto groups = in.add<pe::PlaceGroup>(G);
+    const auto caps = in.add<int32_t>(G);
+    const auto jobs = in.add<pe::PlaceJob>(J, 16);
+    const auto words = in.add<int32_t>(L0 + ND + A + 1);
+    const auto sub = in.add<int32_t>(by_node ? 0 : L0);
+    uint8_t* const h = block_in_host(ctx, in, "placement");
+    fill_place_groups(groups.in(h), G, group_req, group_need, group_count, plan.pod_off.data());
+    if (G > 0) std::memcpy(caps.in(h), sp.cap.data(), caps.bytes());
+    pe::PlaceJob* const h_jobs = jobs.in(h);
     for (int64_t i = 0; i < J; ++i) {
       const int32_t j = plan.jobs[(size_t)i];
       h_jobs[i] = pe::PlaceJob{j, job_group_off[j], job_group_off[j + 1], 0};
     }
-    int32_t* const h_start = pack_domain_words((int32_t*)(h + words_at), plan.leaf_dom, plan.act_of);
+    int32_t* const h_start = pack_domain_words(words.in(h), plan.leaf_dom, plan.act_of);
     std::memcpy(h_start, plan.job_start.data(), (size_t)(A + 1) * sizeof(int32_t));
-    if (!by_node) std::memcpy(h + sub_at, sp.leaf_sub.data(), (size_t)L0 * sizeof(int32_t));
-    hipchk(hipMemcpyAsync(ctx->dm_in.p, h, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D placement inputs");
-    const uint8_t* const d = ctx->dm_in.p;
-    const int32_t* const d_words = (const int32_t*)(d + words_at);
+    if (!by_node) std::memcpy(sub.in(h), sp.leaf_sub.data(), sub.bytes());
+    const uint8_t* const d = block_in_device(ctx, in, "placement");
+    const int32_t* const d_words = words.in(d);
     // ---- the call's device buffers: one block out -- pods [P], statuses [J] -- the logs and the two scratch rows
-    const int64_t n_out = P + J;
-    hipchk(ctx->dm_out.ensure((size_t)n_out * sizeof(int32_t)), "alloc placement outputs");
-    hipchk(ctx->dm_hout.ensure((size_t)n_out * sizeof(int32_t)), "alloc pinned placement outputs");
+    pe::BlockLayout ans;
+    const auto pods = ans.add<int32_t>(P, 4, true);
+    const auto status = ans.add<int32_t>(J, 4, true);
+    uint8_t* const o = block_out_device(ctx, ans, "placement", true);
     hipchk(ctx->dm_log.ensure((size_t)(3 * P)), "alloc placement logs");
-    int32_t* const d_out = (int32_t*)ctx->dm_out.p;
     const pe::PlaceSegs segs = domain_segments(ctx, A);
     const pe::SpreadScratch sc = pe::spread_scratch_layout(segs.seg_stride, by_node);
     hipchk(ctx->dm_scratch.ensure((size_t)((sc.words + 1) / 2)), "alloc allowance rows");
@@ -74,22 +72,18 @@ int pe_place_spread_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
     CapEvents ev(ctx);
     ev.begin();
     launch_domain_members(ctx, d_words, L0, A, segs);
-    hipchk(pe::launch_spread_domains(ctx->stream, (const pe::PlaceGroup*)d, (const int32_t*)(d + caps_at),
-                                     (const pe::PlaceJob*)(d + jobs_at), d_words + L0 + ND, (int)A, segs, ctx->island.p,
-                                     ctx->Ns, by_node ? nullptr : (const int32_t*)(d + sub_at), rows + sc.allow_at,
-                                     rows + sc.sub_at, ctx->res.p, ctx->stride, (uint64_t)ctx->begin, sp.dry_run, d_out,
-                                     d_out + P, ctx->dm_log.p),
+    hipchk(pe::launch_spread_domains(ctx->stream, groups.in(d), caps.in(d), jobs.in(d), d_words + L0 + ND, (int)A, segs,
+                                     ctx->island.p, ctx->Ns, by_node ? nullptr : sub.in(d), rows + sc.allow_at,
+                                     rows + sc.sub_at, ctx->res.p, ctx->stride, (uint64_t)ctx->begin, sp.dry_run,
+                                     pods.in(o), status.in(o), ctx->dm_log.p),
            "launch spread_domains");
     ev.end();
-    hipchk(hipMemcpyAsync(ctx->dm_hout.p, d_out, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream),
-           "D2H placements");
-    hipchk(hipStreamSynchronize(ctx->stream), "sync place_spread_domains");
-    const int32_t* const pods = (const int32_t*)ctx->dm_hout.p;
-    const int32_t* const status = pods + P;
-    if (P > 0) std::memcpy(out_pod_node, pods, (size_t)P * sizeof(int32_t));
-    std::memcpy(out_job_status, status, (size_t)J * sizeof(int32_t));
+    const uint8_t* const a = block_read_back(ctx, ans, "placement", "sync place_spread_domains", "D2H placements");
+    block_part_to(out_pod_node, pods, a);
+    block_part_to(out_job_status, status, a);
     if (!sp.dry_run)
-      mirror_follow(ctx, "spread_domains_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods, status);
+      mirror_follow(ctx, "spread_domains_kernel", J, job_group_off, group_req, plan.pod_off.data(), pods.in(a),
+                    status.in(a));
     ev.report_as("A=" + std::to_string(A));
     return PE_OK;
   });
