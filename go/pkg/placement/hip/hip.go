@@ -1172,6 +1172,34 @@ func (e *Engine) DrainFitDomains(v *Victims, groupNeed []uint32, candNode, candD
 	return fits, moved, failSlot, target, e.err(rc, "pe_drain_fit_domains")
 }
 
+// DrainMoveDomains is DrainFitDomains for a list of nodes that are cordoned together and emptied in order, committed
+// (pe_drain_move_domains): every candNode is out of every decision of the call, candidate c is judged by
+// DrainFitDomains' rule on the residuals as the earlier fitting candidates left them, a candidate that fits stands --
+// its pods' requests come off their targets and go back to its node -- and one that does not leaves its pods where
+// they are.  Arguments and answers as DrainFitDomains; target[s] >= 0 is the new node of slot s.  dryRun answers the
+// same and leaves residuals, mirror and stats as they were.  A sharded engine refuses the call.
+func (e *Engine) DrainMoveDomains(v *Victims, groupNeed []uint32, candNode, candDomain []int32, level int32, levelSize, parent []int32, dryRun bool) (fits []uint8, moved, failSlot []int64, target []int32, err error) {
+	nc := len(candNode)
+	if len(candDomain) != nc {
+		return nil, nil, nil, nil, fmt.Errorf("DrainMoveDomains: %d nodes for %d domains", nc, len(candDomain))
+	}
+	if groupNeed != nil && len(groupNeed) != len(v.GroupCount) {
+		return nil, nil, nil, nil, fmt.Errorf("DrainMoveDomains: %d needs for %d groups", len(groupNeed), len(v.GroupCount))
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_DRAIN_DRY_RUN
+	}
+	fits = make([]uint8, nc)
+	moved = make([]int64, nc)
+	failSlot = make([]int64, nc)
+	target = make([]int32, len(v.PodNode))
+	rc := C.pe_drain_move_domains(e.ctx, C.int64_t(len(v.GroupOff)-1), ptr32(v.GroupOff), ptr32(v.GroupCount), ptr64(v.GroupReq),
+		ptru32(groupNeed), ptr32(v.PodNode), C.int64_t(nc), ptr32(candNode), ptr32(candDomain), C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), flags, ptr8(fits), ptr64(moved), ptr64(failSlot), ptr32(target))
+	return fits, moved, failSlot, target, e.err(rc, "pe_drain_move_domains")
+}
+
 // ScaleUp is ScaleUpDomains' answer: per pair the fewest new nodes (-1 = none up to the pair's maximum), the deciding
 // attempt's failing group (-1 = placed), its pods and those of them on new nodes; per job the pair with the fewest
 // new nodes, ties to the smallest pair, -1 = none.  With selectionOnly the per-pair slices are nil.

@@ -1075,6 +1075,53 @@ int pe_drain_fit_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group
                          uint8_t* out_fits /*[C] or NULL*/, int64_t* out_moved /*[C] or NULL*/,
                          int64_t* out_fail_slot /*[C] or NULL*/, int32_t* out_target /*[S] or NULL*/);
 
+/* (ABI 7, additive) Drain a batch of nodes, moving as it goes: the committing batch form of pe_drain_fit_domains,
+ * as pe_place_preempt_domains is of pe_gang_preempt_domains.  A maintenance window, a firmware roll or an
+ * autoscaler's scale-down cordons a LIST of nodes and empties them in order; with the read-only call that is a chain
+ * per node (pe_drain_fit_domains, pe_release_gangs, pe_assume_gangs), and nothing in the chain keeps node A's pods
+ * off node B, which is next on the list.  NO reference function, as pe_drain_fit_domains.
+ * The book, the candidates, level and hierarchy, runs, island runs as one unit, dom_level(n) and the four outputs
+ * mean what they mean in pe_drain_fit_domains; every cell of out_target is written; each out_* may be NULL.
+ *   Cordon      every cand_node of the call is out of every decision of the call, from its start, whatever its
+ *               position in the list and whether or not its own drain succeeds: "cordon all, then drain one by
+ *               one".  No pod of the call lands on a candidate node, so a candidate's evicted slots are a property
+ *               of the book alone.
+ *   Sequence    candidates are decided in ascending c.  Candidate c is judged by pe_drain_fit_domains' rule for
+ *               (cand_node[c], cand_domain[c]) on the residuals as the earlier FITTING candidates of the call left
+ *               them, with all candidate nodes removed.  A candidate that fits stands: its takes stay.  One that
+ *               does not is rolled back in full and its pods stay where they are; out_moved and out_fail_slot say
+ *               where the rule stopped, as in the what-if, and its targets are -1.  Candidates with different
+ *               target domains touch disjoint nodes: only the order inside one target domain binds.
+ *   Give-back   the node of a candidate that fits gets back the requests of its evicted pods (pe_release_gangs of
+ *               exactly those slots), after every candidate is decided; no decision of the call reads it.  A
+ *               candidate that is a removed slot evicts nothing and fits with 0 pods.
+ * flags: PE_DRAIN_DRY_RUN -- every output is that of the same call without the flag; device residuals, mirror and
+ * pe_stats are untouched.
+ * After a committed call the device residuals and the mirror hold the new state; the reset snapshot, labels,
+ * islands and the staged fit batch are untouched, and so is pe_stats, as with the ledger calls.
+ * Three identities: with one candidate the four outputs are pe_drain_fit_domains'; a dry run followed by the
+ * committed call gives the same outputs twice; and after a committed call, pe_release_gangs of the moved slots at
+ * their targets followed by pe_assume_gangs of the same slots at their old nodes restores the residuals from before.
+ * The example: one rack holds A, B and C.  A holds one 3-GPU pod, B one 2-GPU pod, C has 4 free GPUs; cpu and
+ * memory are ample.  pe_drain_fit_domains of {A, B} says both fit: each is promised C.  pe_drain_move_domains in
+ * the order A, B: A's pod takes C (1 GPU left); B's pod finds nothing -- A is cordoned although it will get 3 GPUs
+ * back.  fits (1, 0), moved (1, 0), fail_slot (-1, B's slot), targets (C, -1).  Afterwards A has 3 more free GPUs,
+ * C has 3 fewer and B is unchanged.
+ * PE_EINVAL, nothing changed and no output written: everything pe_drain_fit_domains refuses, the repeated
+ * cand_node included; unknown flags bits; world_size > 1; and the release bound: whatever pe_release_gangs of ALL
+ * the candidates' evicted slots as one call would refuse against the reset snapshot (products and sums in 128
+ * bits), as pe_place_preempt_domains bounds all its victims.  PE_ESTATE: a call before pe_load_nodes. */
+#define PE_DRAIN_DRY_RUN 1u      /* flags: answer, change nothing */
+int pe_drain_move_domains(pe_ctx* ctx, int64_t n_gangs, const int32_t* gang_group_off /*[V+1]*/,
+                          const int32_t* group_count /*[VG]*/, const int64_t* group_req /*[VG][4]*/,
+                          const uint32_t* group_need /*[VG] or NULL = 0*/,
+                          const int32_t* pod_node /*[S]: global node id per pod slot, -1 = skipped*/,
+                          int64_t n_cands, const int32_t* cand_node /*[C]*/, const int32_t* cand_domain /*[C]*/,
+                          int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                          const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                          uint32_t flags, uint8_t* out_fits /*[C] or NULL*/, int64_t* out_moved /*[C] or NULL*/,
+                          int64_t* out_fail_slot /*[C] or NULL*/, int32_t* out_target /*[S] or NULL*/);
+
 /* (ABI 7, additive) Fewest new nodes for a gang to fit a domain: the question that follows pe_gang_fit_domains' "no"
  * when nothing can be evicted.  How many nodes of THIS node type would have to join THIS rack for the gang to be
  * placed there, and which (node type, rack) choice needs the fewest?  It is the cluster autoscaler's scale-up

@@ -17,6 +17,9 @@ namespace pe_engine {
 void domain_entry_checks(const pe_ctx* ctx, const char* call, int64_t n_jobs);
 // A refused pair list (pe_fit_plan.h FitPlanError, `bad` its index), the hierarchy in raise_tree's words.
 [[noreturn]] void raise_fit_plan(pe::FitPlanError e, pe::TreePlanError te, int64_t bad);
+// A refused drain plan (pe_drain_plan.h DrainPlanError, `bad` its index; pe_engine_drain.cpp), for the two calls built on it.
+[[noreturn]] void raise_drain_plan(pe::DrainPlanError e, pe::GangSlotsError ge, pe::FitPlanError fe, pe::TreePlanError te,
+                                   int64_t bad);
 
 // A refused placing plan (pe_place_plan.h PlacePlanError, `bad` its index), the hierarchy in raise_tree's words.
 [[noreturn]] void raise_place_plan(pe::PlacePlanError e, pe::TreePlanError te, int64_t bad);

@@ -25,6 +25,10 @@ namespace {
   }
 }
 
+}  // namespace
+
+namespace pe_engine {
+
 [[noreturn]] void raise_drain_plan(pe::DrainPlanError e, pe::GangSlotsError ge, pe::FitPlanError fe, pe::TreePlanError te,
                                    int64_t bad) {
   const std::string at = " at index " + std::to_string(bad);
@@ -41,7 +45,7 @@ namespace {
   }
 }
 
-}  // namespace
+}  // namespace pe_engine
 
 extern "C" {
 

@@ -829,6 +829,34 @@ hipError_t launch_drain(hipStream_t s, const PlaceGroup* runs, const DrainPair* 
                         const FitLarge* large, int64_t* scratch, const int32_t* slot_list, const PlaceSegs& segs,
                         const DrainOut& out, bool store);
 
+// ---- drain a batch of nodes, moving as it goes (pe_drain_move_domains, pe_drain_move.hip; the plan:
+// pe_drain_move_plan.h).  The member lists are launch_place_members'; runs, pairs and slot_list as for launch_drain,
+// the pairs in plan order: active domain a's candidates are pairs[pair_start[a] .. pair_start[a + 1]), ascending c.
+struct DrainMoveIn {
+  const PlaceGroup* runs;
+  const DrainPair* pairs;
+  const int32_t* pair_start;   // [A + 1]
+  const int32_t* slot_list;    // [E]
+  const int32_t* run_of;       // [E]: the run of every place of the slot list
+  const int32_t* run_pair;     // [R]: the place in `pairs` of every run's candidate
+  const uint32_t* cordon;      // one bit per node id in [0, n_total), set for the call's candidates
+};
+// cordon (zeroed by the caller) |= the bit of every pairs[0 .. C).node.
+hipError_t launch_drain_cordon(hipStream_t s, const DrainPair* pairs, int64_t C, uint32_t* cordon);
+// One workgroup per active domain a < A, as launch_place_domains: its candidates in plan order on the segment without
+// the cordoned nodes, as the earlier fitting candidates left it.  out: fits, moved and fail_slot (target is the
+// sweep's); moved_row [E]: the node every place of the slot list moved to, -1 = not moved (every cell is written);
+// log: 3 int32 of scratch per place.  dry_run: the answers alone; else the residuals of the segments' nodes that are
+// not cordoned go back to res.
+hipError_t launch_drain_move(hipStream_t s, const DrainMoveIn& in, int A, const PlaceSegs& segs, int64_t* res,
+                             int64_t stride, uint32_t id_base, bool dry_run, const DrainOut& out, int32_t* moved_row,
+                             int32_t* log);
+// After it: target[slot_list[p]] = moved_row[p] for every place (target, where given, set to -1 by the caller) and,
+// unless dry_run, the request of every place of a candidate that fits added to the candidate's node in res.
+hipError_t launch_drain_move_sweep(hipStream_t s, const DrainMoveIn& in, int64_t E, const uint8_t* fits,
+                                   const int32_t* moved_row, int32_t* target, int64_t* res, int64_t stride,
+                                   uint32_t id_base, bool dry_run);
+
 // ---- fewest new nodes for a gang to fit a domain (pe_scale_up_domains, pe_scale.hip; the plan: pe_scale_plan.h;
 // units -- cut by weight -- and FitLarge records as for the fit call).  The member lists are launch_place_members',
 // read-only here.

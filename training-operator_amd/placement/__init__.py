@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SCALE_NODES, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
-                   PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_PREEMPT_DRY_RUN, PE_SPREAD_DRY_RUN,
+                   PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_PREEMPT_DRY_RUN, PE_DRAIN_DRY_RUN, PE_SPREAD_DRY_RUN,
                    PE_SPREAD_NODE, PE_SPREAD_NONE)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
@@ -28,7 +28,7 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "ScaleUp", "PE_MAX_SCALE_NODES", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY",
-           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN"]
+           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN", "PE_DRAIN_DRY_RUN"]
 
 
 class PlacementError(RuntimeError):
@@ -1122,6 +1122,25 @@ class Engine:
         global node id of every pod slot, -1 = skipped) plus group_need; slots on nodes that are no candidate are
         ignored.  level_size / parent describe the hierarchy exactly as for gang_capacity_tree.  Each of the four
         answers can be left out (it then never crosses).  DrainFit.move_of gives the arrays that carry a move out."""
+        return self._drain(None, gang_group_off, group_count, group_req, group_need, pod_node, cand_node, cand_domain,
+                           level, level_size, parent, fits, moved, fail_slot, target)
+
+    def drain_move_domains(self, gang_group_off, group_count, group_req, group_need, pod_node, cand_node, cand_domain,
+                           level, level_size, parent=None, dry_run=False, fits=True, moved=True, fail_slot=True,
+                           target=True) -> DrainFit:
+        """pe_drain_move_domains: drain_fit_domains for a LIST of nodes that are cordoned together and emptied in
+        order, committed.  Every cand_node is out of every decision of the call; candidate c is judged by
+        drain_fit_domains' rule on the residuals as the earlier fitting candidates left them; a candidate that fits
+        stands (its pods' requests come off their targets and go back to its node), one that does not leaves its pods
+        where they are.  Arguments and answer as drain_fit_domains; np.where(answer.target >= 0, answer.target,
+        pod_node) is the book's new pod_node.  dry_run=True (PE_DRAIN_DRY_RUN) gives the same answer and leaves the
+        residuals, the mirror and the stats alone."""
+        return self._drain(PE_DRAIN_DRY_RUN if dry_run else 0, gang_group_off, group_count, group_req, group_need,
+                           pod_node, cand_node, cand_domain, level, level_size, parent, fits, moved, fail_slot, target)
+
+    def _drain(self, move_flags, gang_group_off, group_count, group_req, group_need, pod_node, cand_node, cand_domain,
+               level, level_size, parent, fits, moved, fail_slot, target) -> DrainFit:
+        """The two drain calls' arguments and answers; move_flags None: the read-only call."""
         off = _c(gang_group_off, np.int32).reshape(-1)
         cnt = _c(group_count, np.int32).reshape(-1)
         req = _c(group_req, np.int64).reshape(-1, 4)
@@ -1145,9 +1164,13 @@ class Engine:
         o_moved = np.zeros(C, dtype=np.int64) if moved else None
         o_fail = np.full(C, -1, dtype=np.int64) if fail_slot else None
         o_target = np.full(S, -1, dtype=np.int32) if target else None
-        self._chk(self.lib.pe_drain_fit_domains(self.h, len(off) - 1, _p(off), _p(cnt), _p(req), _p(nd), _p(pod), C, _p(cn),
-                                                _p(cd), int(level), len(ls), _p(ls), _p(par), _p(o_fits), _p(o_moved),
-                                                _p(o_fail), _p(o_target)), "pe_drain_fit_domains")
+        book = (self.h, len(off) - 1, _p(off), _p(cnt), _p(req), _p(nd), _p(pod), C, _p(cn), _p(cd), int(level), len(ls),
+                _p(ls), _p(par))
+        outs = (_p(o_fits), _p(o_moved), _p(o_fail), _p(o_target))
+        if move_flags is None:
+            self._chk(self.lib.pe_drain_fit_domains(*book, *outs), "pe_drain_fit_domains")
+        else:
+            self._chk(self.lib.pe_drain_move_domains(*book, move_flags, *outs), "pe_drain_move_domains")
         return DrainFit(o_fits, o_moved, o_fail, o_target)
 
     def scale_up_domains(self, job_group_off, group_count, group_req, group_need, tmpl_res, tmpl_labels, new_slot,

@@ -34,6 +34,7 @@ PE_MAX_PAIR_VICTIMS = 64
 PE_MAX_SCALE_NODES = 64
 PE_SPREAD_NONE, PE_SPREAD_NODE, PE_SPREAD_DRY_RUN = -1, -1, 1
 PE_PREEMPT_DRY_RUN = 1
+PE_DRAIN_DRY_RUN = 1
 PE_MASK_NODE_TILES, PE_MASK_JOB_BITS, PE_MASK_NODE_BLOCKS, PE_MASK_ROWS = 0, 1, 2, 3
 HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
@@ -115,6 +116,7 @@ SIGNATURES = {
     "pe_release_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_assume_gangs": (ctypes.c_int, [P, i64, P, P, P, P, ctypes.POINTER(i64)]),
     "pe_drain_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
+    "pe_drain_move_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, ctypes.c_uint32, P, P, P, P]),
     "pe_scale_up_domains": (ctypes.c_int, [P, i64, P, P, P, P, i32, P, P, i32, P, i64, P, P, P, P, i32, i32, P, P,
                                            P, P, P, P, P]),
     "pe_resolver_create": (ctypes.c_int, [i64, P, P, P, P, P, ctypes.POINTER(P)]),
