@@ -968,6 +968,27 @@ func (e *Engine) PlaceSpreadDomains(g *Gangs, groupMaxPer []int32, spreadLevel i
 	return podNode, jobStatus, e.err(rc, "pe_place_spread_domains")
 }
 
+// PlaceLeastDomains is PlaceGreedyDomains under the least-allocated rule (kube-scheduler's default
+// NodeResourcesFit strategy, Volcano's leastrequested): each pod goes to the fitting node of its job's domain that
+// keeps the most room, ties to the lowest id, so a group spreads over a levelled rack layer by layer.  dryRun
+// answers and leaves residuals, mirror and stats as they were.  A sharded engine refuses the call.
+func (e *Engine) PlaceLeastDomains(g *Gangs, dryRun bool, jobDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, fmt.Errorf("PlaceLeastDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_LEAST_DRY_RUN
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	rc := C.pe_place_least_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), flags, ptr32(jobDomain), C.int32_t(level), C.int32_t(len(levelSize)),
+		ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus))
+	return podNode, jobStatus, e.err(rc, "pe_place_least_domains")
+}
+
 // MinMemberAll as a minMember: the whole job is mandatory (PE_MIN_MEMBER_ALL).
 const MinMemberAll = int32(C.PE_MIN_MEMBER_ALL)
 

@@ -698,6 +698,46 @@ int pe_place_spread_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_grou
                             const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                             int32_t* out_pod_node, int32_t* out_job_status);
 
+/* (ABI 7, additive) Least-allocated gang placement: pe_place_greedy_domains with the opposite scoring rule, for
+ * clusters that run kube-scheduler's default NodeResourcesFit strategy (LeastAllocated) or Volcano's nodeorder
+ * leastrequested -- parameter servers, data-loader replicas, CPU-side launchers, anything that should not heat one
+ * node while its neighbours idle.  Every other placing call packs (the pod goes to the node that would have the
+ * least left: binpack, MostAllocated); here each pod goes to the fitting node of job_domain[j] with the LARGEST
+ * Appendix-B score after the pod, ties to the lowest node id.  As an argmin:
+ *   least_key(n) = fit ? ((SCORE_MAX - score) << 24) | id : NO_KEY
+ * with fit and score exactly those of the packing key (the same arithmetic, the same
+ * saturation at SCORE_MAX = 2^40 - 1, the same NO_KEY convention: NO_KEY is all ones, so the one fitting node
+ * whose key would equal it -- id 2^24 - 1 with score 0 after the pod, a node the pod fills exactly in every term --
+ * counts as not fitting and is not chosen; the packing key has the same edge at a saturated score).  pe_place_spread_domains does not give this
+ * answer: a cap says how many pods a node may take, not which node takes the next one.
+ * NO reference function, as pe_place_greedy_domains.  Everything not said here means what it means in that call:
+ * jobs in (priority desc, index asc) order, groups in the given order, all-or-nothing with rollback, a
+ * PE_NEED_ISLAND group as one unit of count x request on the argmin-least_key node (a product that overflows fits
+ * nowhere), zero-count groups, a domain without nodes, n_jobs == 0, pod slots in group input order with GLOBAL
+ * node ids, statuses, pe_stats and the host mirror.  Within a group the pod slots are in the order in which the
+ * pod-by-pod rule places them.
+ * The smallest case: a rack of two nodes with 8 free GPUs each, one group of 4 pods x 1 GPU.
+ *   pe_place_greedy_domains   nodes 0, 0, 0, 0
+ *   pe_place_least_domains    nodes 0, 1, 0, 1    (7 and 7 GPUs left after two pods, 6 and 6 after four)
+ * The device does not go pod by pod.  One decision is a ROUND -- every node whose key lies below the smallest key
+ * any node would have after one more pod takes one pod, in key order: a whole layer of a levelled rack -- or a
+ * RUN -- one node takes pods until its key reaches the second smallest key or it no longer fits.  Both equal the
+ * pod-by-pod rule, pod slot for pod slot.
+ * flags: PE_LEAST_DRY_RUN answers and changes nothing -- out_pod_node and out_job_status are those of the same
+ * call without the flag (later jobs of a domain see earlier jobs' takes), while the device residuals, the host
+ * mirror and pe_stats stay as they were: a read-only what-if of a whole batch.
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there is
+ * one): everything pe_place_greedy_domains refuses, unknown flags bits, world_size > 1.  PE_ESTATE: a call before
+ * pe_load_nodes. */
+#define PE_LEAST_DRY_RUN 1u      /* flags: answer, change nothing */
+int pe_place_least_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                           const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                           uint32_t flags,
+                           const int32_t* job_domain /*[J]*/, int32_t level,
+                           int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                           const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                           int32_t* out_pod_node, int32_t* out_job_status);
+
 /* (ABI 7, additive) Exact what-if of a whole gang per domain: would this job, all its groups in order, be
  * placed in this domain right now?  The read-only link between pe_gang_capacity_tree (which domains hold a
  * gang of ONE shape) and pe_place_greedy_domains (which places the gang and changes the residuals).  For a

@@ -655,6 +655,23 @@ hipError_t launch_spread_domains(hipStream_t s, const PlaceGroup* groups, const 
                                  int64_t stride, uint64_t id_base, bool dry_run, int32_t* out_pod, int32_t* out_status,
                                  int32_t* log);
 
+// ---- least-allocated gang placement in rounds (pe_place_least_domains, pe_place_least.hip; the plan:
+// pe_place_plan.h as it is).  The working state of a place grows by one 64-bit key of the rounds' list (48 B per
+// place); the waves' slots carry two keys, theta and the argmin's residuals (488 B).  The LDS instance's limit is
+// the largest segment that keeps the workgroup within the 40 KiB of PL_LDS_NODES' comment:
+// 843 x 48 B + 488 B = 40 952 B.
+constexpr int LS_LDS_NODES = 843;
+// A round ranks its members by comparing every pair: beyond this many (in-place instance only; the LDS instance's
+// segments are smaller) the decision is made as a run, which is exact for every state.
+constexpr uint32_t LS_RANK_MAX = 4096;
+// launch_place_domains under the least-allocated rule.  lists [seg_stride]: scratch, the keys of the rounds of the
+// segments above LS_LDS_NODES nodes.  decisions: one cell the caller zeroes, the decisions made.  dry_run: out_pod
+// and out_status as without it, res left as it is.  The member lists are launch_place_members'.
+hipError_t launch_least_domains(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* job_start,
+                                int A, const PlaceSegs& segs, uint64_t* lists, int64_t* res, int64_t stride,
+                                uint64_t id_base, bool dry_run, int32_t* out_pod, int32_t* out_status, int32_t* log,
+                                unsigned long long* decisions);
+
 // ---- first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_place.hip; the plan:
 // pe_first_fit_plan.h).  The member lists are launch_place_members'; the segments stay the working residuals of
 // their domains from round to round.
