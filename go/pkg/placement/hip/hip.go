@@ -1365,3 +1365,45 @@ func (r *Resolver) Results() (podNode, jobStatus []int32, err error) {
 	}
 	return podNode, jobStatus, nil
 }
+
+// SkewNone as a maxSkew: no constraint (PE_SKEW_NONE).
+const SkewNone = int32(C.PE_SKEW_NONE)
+
+// SkewBook is the existing pods a spread constraint counts: entry e in [GroupOff[g], GroupOff[g+1]) says that spread
+// domain Dom[e] -- a global node id for SpreadNode, a domain of the spread level otherwise -- already holds Count[e]
+// pods that group g's selector matches.  Duplicates add up; entries outside the job's domain are ignored.
+type SkewBook struct {
+	GroupOff, Dom, Count []int32
+}
+
+// PlaceSkewDomains is PlaceGreedyDomains under topologySpreadConstraints' maxSkew with whenUnsatisfiable:
+// DoNotSchedule, on hostname (spreadLevel SpreadNode) or on a rack key (spreadLevel below level).  groupMaxSkew is [G]
+// (nil or SkewNone: no constraint); book may be nil.  dryRun answers and leaves residuals, mirror and stats as they
+// were.  A sharded engine refuses the call.
+func (e *Engine) PlaceSkewDomains(g *Gangs, groupMaxSkew []int32, spreadLevel int32, book *SkewBook, dryRun bool, jobDomain []int32, level int32, levelSize, parent []int32) (podNode, jobStatus []int32, err error) {
+	J := len(g.JobGroupOff) - 1
+	if groupMaxSkew != nil && len(groupMaxSkew) != len(g.GroupCount) {
+		return nil, nil, fmt.Errorf("PlaceSkewDomains: %d skews for %d groups", len(groupMaxSkew), len(g.GroupCount))
+	}
+	if jobDomain != nil && len(jobDomain) != J {
+		return nil, nil, fmt.Errorf("PlaceSkewDomains: %d domains for %d jobs", len(jobDomain), J)
+	}
+	var off, dom, count []int32
+	if book != nil {
+		off, dom, count = book.GroupOff, book.Dom, book.Count
+		if len(off) != len(g.GroupCount)+1 || len(dom) != len(count) || int(off[len(off)-1]) > len(dom) {
+			return nil, nil, fmt.Errorf("PlaceSkewDomains: book of %d offsets, %d domains, %d counts for %d groups", len(off), len(dom), len(count), len(g.GroupCount))
+		}
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_SKEW_DRY_RUN
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	rc := C.pe_place_skew_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), ptr32(groupMaxSkew), C.int32_t(spreadLevel), ptr32(off), ptr32(dom),
+		ptr32(count), flags, ptr32(jobDomain), C.int32_t(level), C.int32_t(len(levelSize)), ptr32(levelSize),
+		ptr32(parent), ptr32(podNode), ptr32(jobStatus))
+	return podNode, jobStatus, e.err(rc, "pe_place_skew_domains")
+}

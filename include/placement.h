@@ -738,6 +738,62 @@ int pe_place_least_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group
                            const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                            int32_t* out_pod_node, int32_t* out_job_status);
 
+/* (ABI 7, additive) Gang placement under maxSkew spread: pe_place_greedy_domains for pod templates that carry
+ * topologySpreadConstraints with maxSkew and whenUnsatisfiable: DoNotSchedule on hostname or on a rack key -- elastic
+ * PyTorchJobs, parameter-server sets, data-loader sets.  A cap (pe_place_spread_domains) is not that rule: it cannot
+ * see a full rack that keeps the minimum down, and it cannot balance against pods that already run.  NO reference
+ * function, as pe_place_greedy_domains.  Everything not said here means what it means in that call: jobs in (priority
+ * desc, index asc) order, groups in the given order, all-or-nothing with rollback, pod slots in group input order with
+ * GLOBAL node ids, zero-count groups, a domain without nodes, n_jobs == 0, statuses, pe_stats and the host mirror.
+ * The spread domain sd(n) of node n is n itself when spread_level == PE_SPREAD_NODE, else dom_{spread_level}(n) with
+ * 0 <= spread_level < level, as in pe_place_spread_domains.
+ * The book of existing pods: entry e in [group_base_off[g], group_base_off[g + 1]) says that spread domain base_dom[e]
+ * -- a global node id for PE_SPREAD_NODE, a level-`spread_level` domain id otherwise -- already holds base_count[e]
+ * pods that the constraint's selector matches.  Duplicates add up (a sum stops at 2^31 - 1).  An entry whose spread
+ * domain does not lie under job_domain[j] is ignored: such pods sit on nodes the job may not use.  group_base_off
+ * NULL: no pods anywhere.
+ * Eligible spread domains: for group g of job j, a spread domain u under job_domain[j] is ELIGIBLE if it has at least
+ * one node n of the inventory with (lab(n) & need) == need.  Resource fit does not matter (the scheduler's
+ * node-affinity policy Honor): a full rack is still eligible and keeps the minimum down; a rack without a matching
+ * node is not, and neither holds the minimum down nor counts its book entries.
+ * The rule: group g with s = group_max_skew[g] places its pods one at a time.  cnt[u] = the book's pods of u + the
+ * pods of this group placed in u by this call; gmin = the minimum of cnt over the eligible spread domains; the pod
+ * goes to the argmin-key node among the nodes of job_domain[j] that fit and have cnt[sd(n)] + 1 - gmin <= s, and
+ * cnt[sd(n)] += 1.  No such node: the gang is PE_JOB_UNSCHEDULABLE and rolled back.  The counts are per group: other
+ * groups' and other jobs' pods from this call are not in them.  A PE_NEED_ISLAND group is one unit on one node: it
+ * needs the count x request fit and cnt[u] + count - m_other(u) <= s, m_other(u) = the minimum over the eligible
+ * spread domains other than u (none: nothing bounds u).  PE_SKEW_NONE (or group_max_skew NULL) is no constraint;
+ * with every group unconstrained the call is pe_place_greedy_domains, output for output and residual for residual.
+ * The smallest case: a rack of two nodes with 8 free GPUs each, one group of 4 pods x 1 GPU, PE_SPREAD_NODE.
+ *   maxSkew 1                        nodes 0, 1, 0, 1
+ *   maxSkew 2                        nodes 0, 0, 1, 0   (the third pod lifts gmin to 1, so node 0 may hold a third)
+ *   maxSkew 1, book {node 1: 2}      nodes 0, 0, 0, 1
+ *   maxSkew 1, node 1 full (0 GPUs)  PE_JOB_UNSCHEDULABLE: node 1 stays eligible with 0 pods, the second pod has no
+ *                                    node.  pe_place_spread_domains with a cap of 4 places all four on node 0.
+ * The device does not go pod by pod.  It keeps the smallest count, how many spread domains hold it and the next
+ * count; from them every node knows how many pods in a row its spread domain may take, and one decision takes
+ * min(what the node holds, that allowance, pods left) -- or a single pod while the only minimum is being filled and
+ * a better-scoring node waits to be let in.  Both equal the pod-by-pod rule, pod slot for pod slot.
+ * Out of scope: minDomains, and whenUnsatisfiable: ScheduleAnyway, which is a score and not a fit.
+ * flags: PE_SKEW_DRY_RUN answers and changes nothing, with PE_SPREAD_DRY_RUN's contract.
+ * PE_EINVAL, nothing changed and no output written (the first offending index in pe_last_error where there is one),
+ * checked in this order: everything pe_place_greedy_domains refuses, spread_level < -1 or >= level, a
+ * group_max_skew[g] of 0 or below -1, a negative or descending group_base_off (or entries without base_dom or
+ * base_count), a base_dom[e] outside its level (outside [0, N) for nodes), a negative base_count[e], unknown flags
+ * bits; world_size > 1.  PE_ESTATE: a call before pe_load_nodes. */
+#define PE_SKEW_NONE (-1)        /* group_max_skew[g]: no constraint */
+#define PE_SKEW_DRY_RUN 1u       /* flags: answer, change nothing */
+int pe_place_skew_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                          const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                          const int32_t* group_max_skew /*[G], or NULL = every group PE_SKEW_NONE*/,
+                          int32_t spread_level,
+                          const int32_t* group_base_off /*[G + 1], or NULL = no existing pods*/,
+                          const int32_t* base_dom, const int32_t* base_count, uint32_t flags,
+                          const int32_t* job_domain /*[J]*/, int32_t level,
+                          int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                          const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                          int32_t* out_pod_node, int32_t* out_job_status);
+
 /* (ABI 7, additive) Exact what-if of a whole gang per domain: would this job, all its groups in order, be
  * placed in this domain right now?  The read-only link between pe_gang_capacity_tree (which domains hold a
  * gang of ONE shape) and pe_place_greedy_domains (which places the gang and changes the residuals).  For a

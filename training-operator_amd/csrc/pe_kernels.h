@@ -672,6 +672,26 @@ hipError_t launch_least_domains(hipStream_t s, const PlaceGroup* groups, const P
                                 uint64_t id_base, bool dry_run, int32_t* out_pod, int32_t* out_status, int32_t* log,
                                 unsigned long long* decisions);
 
+// ---- gang placement under maxSkew spread (pe_place_skew_domains, pe_place_skew.hip; the plan: pe_skew_plan.h).
+// The working state of a place grows by its spread domain's first place and its spread domain's pod count (two
+// words: 48 B per place), one instance for both kinds of spread domain; the waves' slots carry the family's, two
+// argmins and the scan of the counts (400 B).  The LDS instance's limit is the largest segment that keeps the
+// workgroup within the 40 KiB of PL_LDS_NODES' comment: 845 x 48 B + 400 B = 40 960 B.
+constexpr int SK_LDS_NODES = 845;
+// launch_place_domains under the groups' maxSkew: skew[G] (>= 1; 0: no constraint), the book of existing pods
+// book_off[G + 1] / book[E][2] = (key, pods) with a group's keys distinct.  leaf_sd == NULL: the spread domain is the
+// node and a key a global node id; else leaf_sd[n_leaf] is the plan's (island [Ns]: the nodes' leaves) and a key a
+// domain of the spread level.  constrained: some skew is not 0 -- only then sub_row [seg_stride], cnt_row
+// [seg_stride] and where [n_keys] (scratch, all three) are written and read.  decisions: one cell the caller zeroes,
+// the takes made.  dry_run: out_pod and out_status as without it, res left as it is.  The member lists are
+// launch_place_members'.
+hipError_t launch_skew_domains(hipStream_t s, const PlaceGroup* groups, const PlaceJob* jobs, const int32_t* job_start,
+                               int A, const PlaceSegs& segs, const int32_t* island, int64_t Ns, const int32_t* leaf_sd,
+                               const int32_t* skew, const int32_t* book_off, const int32_t* book, bool constrained,
+                               uint32_t* sub_row, uint32_t* cnt_row, int32_t* where, int64_t n_keys, int64_t* res,
+                               int64_t stride, uint64_t id_base, bool dry_run, int32_t* out_pod, int32_t* out_status,
+                               int32_t* log, unsigned long long* decisions);
+
 // ---- first-fit placement of a batch over candidate domains (pe_place_first_fit_domains, pe_place.hip; the plan:
 // pe_first_fit_plan.h).  The member lists are launch_place_members'; the segments stay the working residuals of
 // their domains from round to round.

@@ -18,7 +18,7 @@ import numpy as np
 from . import _abi
 from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SCALE_NODES, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_PREEMPT_DRY_RUN, PE_DRAIN_DRY_RUN, PE_SPREAD_DRY_RUN, PE_LEAST_DRY_RUN,
-                   PE_SPREAD_NODE, PE_SPREAD_NONE)
+                   PE_SPREAD_NODE, PE_SPREAD_NONE, PE_SKEW_NONE, PE_SKEW_DRY_RUN)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
 
@@ -28,7 +28,7 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "ScaleUp", "PE_MAX_SCALE_NODES", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY",
-           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN", "PE_DRAIN_DRY_RUN", "PE_LEAST_DRY_RUN"]
+           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN", "PE_DRAIN_DRY_RUN", "PE_LEAST_DRY_RUN", "PE_SKEW_NONE", "PE_SKEW_DRY_RUN"]
 
 
 class PlacementError(RuntimeError):
@@ -958,6 +958,41 @@ class Engine:
         self._chk(self.lib.pe_place_least_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
                                                   _p(nd), PE_LEAST_DRY_RUN if dry_run else 0, _p(dom), int(level),
                                                   len(ls), _p(ls), _p(par), _p(pod), _p(st)), "pe_place_least_domains")
+        return pod[:P], st[:J]
+
+    def place_skew_domains(self, job_group_off, priority, group_count, group_req, group_need, group_max_skew,
+                           spread_level, job_domain, level, level_size, parent=None, base=None, dry_run=False):
+        """pe_place_skew_domains: place_greedy_domains under topologySpreadConstraints' maxSkew (DoNotSchedule).
+        group_max_skew [G]: >= 1 (PE_SKEW_NONE = -1 or None: no constraint); spread_level: PE_SPREAD_NODE = -1 for
+        hostname, else a level below `level`.  base: the existing pods the constraint counts, as (group_base_off
+        [G + 1], base_dom, base_count) -- base_dom a node id or a domain of the spread level -- or None.  dry_run:
+        the answer of the call, with residuals, mirror and stats left as they were.  Returns (pod_node, job_status)."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        skew = None if group_max_skew is None else _c(group_max_skew, np.int32)
+        if skew is not None and skew.shape != cnt.shape:
+            raise ValueError("group_max_skew must be [G]")
+        boff, bdom, bcnt = (None, None, None) if base is None else (_c(x, np.int32).reshape(-1) for x in base)
+        if boff is not None and (boff.shape != (len(cnt) + 1,) or bdom.shape != bcnt.shape or
+                                 (len(boff) and not 0 <= int(boff.max()) <= len(bdom))):
+            raise ValueError("base must be (group_base_off [G + 1], base_dom [E], base_count [E])")
+        dom = None if job_domain is None else _c(job_domain, np.int32)
+        if dom is not None and dom.shape != (J,):
+            raise ValueError("job_domain must be [J]")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        self._chk(self.lib.pe_place_skew_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
+                                                 _p(nd), _p(skew), int(spread_level), _p(boff), _p(bdom), _p(bcnt),
+                                                 PE_SKEW_DRY_RUN if dry_run else 0, _p(dom), int(level), len(ls),
+                                                 _p(ls), _p(par), _p(pod), _p(st)), "pe_place_skew_domains")
         return pod[:P], st[:J]
 
     def place_min_member_domains(self, job_group_off, priority, group_count, group_req, group_need, min_member,

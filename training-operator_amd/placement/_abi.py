@@ -36,6 +36,7 @@ PE_SPREAD_NONE, PE_SPREAD_NODE, PE_SPREAD_DRY_RUN = -1, -1, 1
 PE_PREEMPT_DRY_RUN = 1
 PE_DRAIN_DRY_RUN = 1
 PE_LEAST_DRY_RUN = 1
+PE_SKEW_NONE, PE_SKEW_DRY_RUN = -1, 1
 PE_MASK_NODE_TILES, PE_MASK_JOB_BITS, PE_MASK_NODE_BLOCKS, PE_MASK_ROWS = 0, 1, 2, 3
 HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
@@ -108,6 +109,7 @@ SIGNATURES = {
     "pe_place_greedy_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, P, P]),
     "pe_place_spread_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, ctypes.c_uint32, P, i32, i32, P, P, P, P]),
     "pe_place_least_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, ctypes.c_uint32, P, i32, i32, P, P, P, P]),
+    "pe_place_skew_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, P, P, P, ctypes.c_uint32, P, i32, i32, P, P, P, P]),
     "pe_place_min_member_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_gang_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
