@@ -1063,6 +1063,41 @@ func (e *Engine) PlaceFirstFitDomains(g *Gangs, pairJob, pairDomain []int32, lev
 	return podNode, jobStatus, jobPair, e.err(rc, "pe_place_first_fit_domains")
 }
 
+// Cells of PlaceBestFitDomains' pairSlots for a pair without slots: the job does not fit the pair's domain, or an
+// earlier pair of the job names the domain already.
+const (
+	PairNoFit  = int64(C.PE_PAIR_NO_FIT)
+	PairRepeat = int64(C.PE_PAIR_REPEAT)
+)
+
+// PlaceBestFitDomains is PlaceFirstFitDomains under the tightest-domain rule (Kueue's topology-aware scheduling,
+// Volcano's HyperNode binpack): every job, in (priority desc, index asc) order, is placed in the candidate domain in
+// which PlaceGreedyDomains would place it against the residuals as the earlier jobs left them and which holds the
+// fewest slots for its reference group -- its group with the most pods --, ties to the smallest pair.  jobPair[j] is
+// the pair that placed job j or -1; pairSlots[p] the slots of pair p where the job fits, PairNoFit where it does not,
+// PairRepeat for a repeated domain.  dryRun answers and leaves residuals, mirror and stats as they were.  A sharded
+// engine refuses the call.
+func (e *Engine) PlaceBestFitDomains(g *Gangs, pairJob, pairDomain []int32, dryRun bool, level int32, levelSize, parent []int32) (podNode, jobStatus, jobPair []int32, pairSlots []int64, err error) {
+	J := len(g.JobGroupOff) - 1
+	P := len(pairJob)
+	if len(pairDomain) != P {
+		return nil, nil, nil, nil, fmt.Errorf("PlaceBestFitDomains: %d jobs for %d domains", P, len(pairDomain))
+	}
+	flags := C.uint32_t(0)
+	if dryRun {
+		flags = C.PE_BEST_DRY_RUN
+	}
+	podNode = make([]int32, g.pods())
+	jobStatus = make([]int32, J)
+	jobPair = make([]int32, J)
+	pairSlots = make([]int64, P)
+	rc := C.pe_place_best_fit_domains(e.ctx, C.int64_t(J), ptr32(g.JobGroupOff), ptr32(g.Priority), ptr32(g.GroupCount),
+		ptr64(g.GroupReq), ptru32(g.GroupNeed), C.int64_t(P), ptr32(pairJob), ptr32(pairDomain), flags, C.int32_t(level),
+		C.int32_t(len(levelSize)), ptr32(levelSize), ptr32(parent), ptr32(podNode), ptr32(jobStatus), ptr32(jobPair),
+		ptr64(pairSlots))
+	return podNode, jobStatus, jobPair, pairSlots, e.err(rc, "pe_place_best_fit_domains")
+}
+
 // Victims are placed gangs in the shape the placement calls take and return: victim v has the groups
 // [GroupOff[v], GroupOff[v+1]) with GroupCount pods of GroupReq each ([VG][4], flattened), and PodNode holds the
 // global node id of every pod slot, groups in input order, -1 for a slot that was skipped.

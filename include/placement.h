@@ -881,6 +881,52 @@ int pe_place_first_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_g
                                const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
                                int32_t* out_pod_node, int32_t* out_job_status, int32_t* out_job_pair /*[J] or NULL*/);
 
+/* (ABI 7, additive) Best-fit placement of a batch over candidate domains: place each gang in the candidate domain
+ * that fits it most tightly.  pe_gang_capacity_domains / _tree pick the domain with the smallest slots >= count
+ * "so that large domains stay free for large gangs", but judge every job against the same untouched residuals;
+ * pe_place_first_fit_domains is exact for a batch, but takes the candidates in list order.  This call does both:
+ * the tightest-rack rule of Kueue's topology-aware scheduling and of Volcano's HyperNode binpack, exact for a
+ * batch.  NO reference function, as pe_place_greedy_domains.  Everything not said here means what it means in
+ * pe_place_first_fit_domains: the job order (priority desc, index asc) and the groups, island groups, a pair in
+ * any order and ungrouped, a job in no pair, the refusals, pe_stats, the host mirror, the staged fit batch, and
+ * world_size > 1 -> PE_EINVAL.
+ * The REFERENCE GROUP of job j is its group with the largest group_count, ties to the first; a job with no pods
+ * has none.
+ * The score of a pair: slots(p) = sum over the nodes n of pair_domain[p] at `level` of cap(n), with cap(n) exactly
+ * as pe_gang_capacity defines it for the reference group's request and its label bits -- PE_NEED_ISLAND masked
+ * off, saturating at PE_CAP_MAX per node --, against the residuals AS THEY STAND WHEN JOB j's TURN COMES; 0 with no
+ * reference group.
+ * The choice: pair p FITS if pe_place_greedy_domains on the single job j with job_domain = pair_domain[p] would
+ * place the job against those residuals.  Job j is placed in the fitting pair with the smallest slots(p), ties to
+ * the smallest p; if no pair fits it is PE_JOB_UNSCHEDULABLE with -1 in every pod slot and out_job_pair[j] = -1.
+ *   out_pair_slots[p] = slots(p) if pair p fits, PE_PAIR_NO_FIT if it does not, PE_PAIR_REPEAT if an earlier pair
+ *                       of the same job names the same domain (such a pair can never win a tie and is never
+ *                       evaluated)
+ * The smallest case: rack A has two nodes with 8 free GPUs each (16 slots for a 1-GPU pod), rack B one such node
+ * (8 slots).  Job 0 is 4 pods x 1 GPU, job 1 is 16 pods x 1 GPU with lower priority; both list [A, B].
+ *   pe_place_first_fit_domains   job 0 in A (12 left), job 1 fits nowhere
+ *   pe_place_best_fit_domains    job 0 in B (8 >= 4 is the smallest fit), job 1 in A: both placed
+ * Two identities follow: with exactly one pair per job every output equals pe_place_greedy_domains with
+ * job_domain[j] = pair_domain[pair of j], output for output; with one job in the call out_job_pair[0] is the
+ * argmin (ties to the smallest p) of pe_gang_capacity_domains' slots for the reference group over the pairs for
+ * which pe_gang_fit_domains says "fits".
+ * flags: PE_BEST_DRY_RUN answers and changes nothing -- every output is that of the same call without the flag
+ * (later jobs see earlier jobs' takes), while the device residuals, the host mirror and pe_stats stay as they were.
+ * Unknown flags bits are PE_EINVAL.
+ * The device runs the rule exactly, in rounds of one launch each, one workgroup per active domain; a workgroup
+ * never waits for another.  At most n_pairs + n_jobs + 1 rounds are launched; a batch
+ * that were not settled by then is PE_EHIP (never seen: the bound is proven). */
+#define PE_BEST_DRY_RUN 1u       /* flags: answer, change nothing */
+#define PE_PAIR_NO_FIT (-1)      /* out_pair_slots[p]: the job does not fit the pair's domain */
+#define PE_PAIR_REPEAT (-2)      /* out_pair_slots[p]: an earlier pair of the job names the domain */
+int pe_place_best_fit_domains(pe_ctx* ctx, int64_t n_jobs, const int32_t* job_group_off, const int32_t* priority,
+                              const int32_t* group_count, const int64_t* group_req, const uint32_t* group_need /* or NULL = 0 */,
+                              int64_t n_pairs, const int32_t* pair_job /*[P]*/, const int32_t* pair_domain /*[P]*/,
+                              uint32_t flags, int32_t level, int32_t n_levels, const int32_t* level_size /*[n_levels]*/,
+                              const int32_t* parent /* as pe_gang_capacity_tree; NULL allowed when n_levels == 1 */,
+                              int32_t* out_pod_node, int32_t* out_job_status, int32_t* out_job_pair /*[J] or NULL*/,
+                              int64_t* out_pair_slots /*[P] or NULL*/);
+
 /* (ABI 7, additive) Which gangs must go for a gang to fit: the question behind pe_gang_fit_domains' "no".  A
  * high-priority job finds its racks full; which of the lower-priority gangs already placed there would have
  * to be evicted for it to be placed in this rack, and which candidate rack needs the fewest evictions?  The

@@ -726,6 +726,43 @@ hipError_t launch_first_fit_round(hipStream_t s, const PlaceGroup* groups, const
 hipError_t launch_first_fit_finish(hipStream_t s, const PlaceSegs& segs, int A, int64_t Ns, int64_t* res, int64_t stride,
                                    uint64_t id_base);
 
+// ---- best-fit placement of a batch over candidate domains (pe_place_best_fit_domains, pe_place_best_fit.hip; the
+// plan: pe_best_fit_plan.h).  The member lists, the segments and the last write-back are first fit's.  The working
+// state of a place is pe_place.hip's 40 B; the head of a queue needs 72 B beside the waves' minima, so the LDS
+// instance keeps PL_LDS_NODES: 1016 x 40 B + 128 B + 72 B = 40 840 B, within the 40 KiB of PL_LDS_NODES' comment.
+// One entry of an active domain's queue: the kept pair `pair` of `job`.  A queue is sorted by the job's rank.
+struct BestFitEntry {
+  int32_t job, pair;
+};
+static_assert(sizeof(BestFitEntry) == 8, "BestFitEntry must be 8 B");
+// One job, by the caller's index: its groups [g0, g1), its reference group (an index into the groups, -1: none) and
+// its kept pairs kept[k0 .. k1), ascending.
+struct BestFitJob {
+  int32_t g0, g1, ref, k0, k1, pad_[3];
+};
+static_assert(sizeof(BestFitJob) == 32, "BestFitJob must be 32 B");
+// The state the rounds carry.  ev_round[P]: the round that evaluated pair p, 0 before; ev_slots[P]: what it found,
+// slots(p) or -1 where the job does not fit -- the caller zeroes the one and fills the other with -1, and after the
+// last round ev_slots is the call's out_pair_slots but for the repeats.  cursor[A]: per active domain the next entry
+// of its queue, set to q_start[a] by the caller.  open: the jobs not yet settled, set by the caller to the number of
+// jobs with a pair.
+struct BestFitState {
+  uint32_t* ev_round;
+  long long* ev_slots;
+  int32_t* cursor;
+  uint32_t* open;
+};
+// Round `round` (1, 2, ...): one workgroup per active domain looks at the head of its queue.  A head not yet
+// evaluated is evaluated -- its slots and a what-if of the job on a copy of the segment -- and ends the round for
+// the domain; a head evaluated in an earlier round is decided once every kept pair of its job was evaluated BEFORE
+// THIS ROUND: the domain of the tightest fitting pair places the job, every other domain passes the entry by.
+// shadow [4][seg_stride]: scratch, the copies of the segments above PL_LDS_NODES nodes.  out_pod [P] and out_pair [J]
+// preset to -1 and out_status [J] to 1 by the caller; log, kinds as for launch_first_fit_round.
+hipError_t launch_best_fit_round(hipStream_t s, const PlaceGroup* groups, const BestFitJob* jobs, const int32_t* kept,
+                                 const int32_t* q_start, const BestFitEntry* queue, int A, const PlaceSegs& segs,
+                                 int64_t* shadow, int kinds, uint32_t round, const BestFitState& st, int32_t* out_pod,
+                                 int32_t* out_status, int32_t* out_pair, int32_t* log);
+
 // ---- exact what-if of a whole gang per domain (pe_gang_fit_domains, pe_fit.hip; the plan and its FitUnit /
 // FitLarge records: pe_fit_plan.h).  The member lists are launch_place_members', read-only here.
 struct FitUnit;

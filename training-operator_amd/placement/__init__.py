@@ -18,7 +18,8 @@ import numpy as np
 from . import _abi
 from ._abi import (PE_CAP_MAX, PE_MAX_DOMAINS, PE_MAX_LEVELS, PE_MAX_PAIR_VICTIMS, PE_MAX_SCALE_NODES, PE_MAX_SPLIT_PARTS, PE_SPLIT_TOO_MANY, PE_SLICE_NODE, PE_JOB_PLACED, PE_JOB_UNSCHEDULABLE, PE_KIND_CONTAINER, PE_KIND_INIT, PE_KIND_OVERHEAD,
                    PE_KIND_SHIFT, PE_KIND_SIDECAR, PE_MODE_V1, PE_MODE_V2, PE_NODE_REMOVE, PE_NODE_SET, PE_PREEMPT_DRY_RUN, PE_DRAIN_DRY_RUN, PE_SPREAD_DRY_RUN, PE_LEAST_DRY_RUN,
-                   PE_SPREAD_NODE, PE_SPREAD_NONE, PE_SKEW_NONE, PE_SKEW_DRY_RUN)
+                   PE_SPREAD_NODE, PE_SPREAD_NONE, PE_SKEW_NONE, PE_SKEW_DRY_RUN, PE_BEST_DRY_RUN, PE_PAIR_NO_FIT,
+                   PE_PAIR_REPEAT)
 
 V1, V2 = PE_MODE_V1, PE_MODE_V2
 
@@ -28,7 +29,8 @@ __all__ = ["Engine", "HostExchange", "Resolver", "PlacementError", "V1", "V2", "
            "select_domain", "PE_MAX_LEVELS", "TreeCapacity", "select_tree", "GangFit", "DrainFit", "ScaleUp", "PE_MAX_SCALE_NODES", "GangPreempt", "PE_MAX_PAIR_VICTIMS",
            "TreeSplit", "split_tree", "PE_MAX_SPLIT_PARTS", "PE_SPLIT_TOO_MANY", "TreeSlices", "PE_SLICE_NODE",
            "FitExplain", "explain_message", "PE_EXPLAIN_BINS", "PE_EXPLAIN_LABELS", "PE_EXPLAIN_ANY",
-           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN", "PE_DRAIN_DRY_RUN", "PE_LEAST_DRY_RUN", "PE_SKEW_NONE", "PE_SKEW_DRY_RUN"]
+           "PE_SPREAD_NONE", "PE_SPREAD_NODE", "PE_SPREAD_DRY_RUN", "PlacePreempt", "PE_PREEMPT_DRY_RUN", "PE_DRAIN_DRY_RUN", "PE_LEAST_DRY_RUN", "PE_SKEW_NONE", "PE_SKEW_DRY_RUN",
+           "PE_BEST_DRY_RUN", "PE_PAIR_NO_FIT", "PE_PAIR_REPEAT"]
 
 
 class PlacementError(RuntimeError):
@@ -1303,6 +1305,38 @@ class Engine:
                                                       _p(nd), len(pj), _p(pj), _p(pd), int(level), len(ls), _p(ls),
                                                       _p(par), _p(pod), _p(st), _p(jp)), "pe_place_first_fit_domains")
         return pod[:P], st[:J], (jp[:J] if pairs else None)
+
+    def place_best_fit_domains(self, job_group_off, priority, group_count, group_req, group_need, pair_job,
+                               pair_domain, level, level_size, parent=None, dry_run=False):
+        """pe_place_best_fit_domains: every job, in (priority desc, index asc) order, is placed in the candidate
+        domain that fits it -- place_greedy_domains would place it there against the residuals as the earlier jobs
+        left them -- and holds the fewest slots for its reference group (its largest group), ties to the smallest
+        pair.  dry_run: the answer of the call, with residuals, mirror and stats left as they were.  Returns
+        (pod_node, job_status, job_pair, pair_slots): pair_slots[p] is the slots of pair p where the job fits,
+        PE_PAIR_NO_FIT where it does not, PE_PAIR_REPEAT for a pair whose domain an earlier pair of the job names."""
+        jgo = _c(job_group_off, np.int32)
+        J = len(jgo) - 1
+        cnt = _c(group_count, np.int32)
+        req = _c(group_req, np.int64).reshape(-1, 4)
+        nd = None if group_need is None else _c(group_need, np.uint32)
+        pj = _c(pair_job, np.int32).reshape(-1)
+        pd = _c(pair_domain, np.int32).reshape(-1)
+        if pj.shape != pd.shape:
+            raise ValueError("pair_job and pair_domain must have one length")
+        if level_size is None:
+            raise ValueError("level_size is required")
+        ls = _c(level_size, np.int32).reshape(-1)
+        par = None if parent is None else _c(parent, np.int32).reshape(-1)
+        P = int(np.clip(cnt, 0, None).astype(np.int64).sum())
+        pod = np.full(max(P, 1), -1, dtype=np.int32)
+        st = np.zeros(max(J, 1), dtype=np.int32)
+        jp = np.full(max(J, 1), -1, dtype=np.int32)
+        sl = np.full(max(len(pj), 1), PE_PAIR_NO_FIT, dtype=np.int64)
+        self._chk(self.lib.pe_place_best_fit_domains(self.h, J, _p(jgo), _p(_c(priority, np.int32)), _p(cnt), _p(req),
+                                                     _p(nd), len(pj), _p(pj), _p(pd), PE_BEST_DRY_RUN if dry_run else 0,
+                                                     int(level), len(ls), _p(ls), _p(par), _p(pod), _p(st), _p(jp),
+                                                     _p(sl)), "pe_place_best_fit_domains")
+        return pod[:P], st[:J], jp[:J], sl[:len(pj)]
 
     # ------------------------------------------------------------ misc
     def synchronize(self):

@@ -37,6 +37,7 @@ PE_PREEMPT_DRY_RUN = 1
 PE_DRAIN_DRY_RUN = 1
 PE_LEAST_DRY_RUN = 1
 PE_SKEW_NONE, PE_SKEW_DRY_RUN = -1, 1
+PE_BEST_DRY_RUN, PE_PAIR_NO_FIT, PE_PAIR_REPEAT = 1, -1, -2
 PE_MASK_NODE_TILES, PE_MASK_JOB_BITS, PE_MASK_NODE_BLOCKS, PE_MASK_ROWS = 0, 1, 2, 3
 HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
@@ -113,6 +114,8 @@ SIGNATURES = {
     "pe_place_min_member_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_gang_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P, P]),
     "pe_place_first_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, i32, i32, P, P, P, P, P]),
+    "pe_place_best_fit_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, i64, P, P, ctypes.c_uint32, i32, i32, P, P, P, P,
+                                                 P, P]),
     "pe_gang_preempt_domains": (ctypes.c_int, [P, i64, P, P, P, P, i64, P, P, P, P, i64, P, P, P, P, i32, i32, P, P,
                                                P, P, P, P]),
     "pe_place_preempt_domains": (ctypes.c_int, [P, i64, P, P, P, P, P, P, i32, i32, P, P, i64, P, P, P, P, P, P,
